@@ -18,10 +18,19 @@ of it at 1.25 M pairs -- runs beside the start of the next; the line also carrie
 default is one in flight, and the roofline's launch durations are those of launches that have the chip to themselves.
 
 Rank 0 prints ONE JSON line.  `value` = whole-job GCUPS = sum(tl*ql) over all ranks and steps /
-max-over-ranks wall time.  `roofline` prices the dominant kernel (sw_dp_kernel) against HBM
-bandwidth with the algorithmic bytes of DESIGN.md; `cpu_baseline` is the reference's own AVX2
-path (oracle/_ref, built from /root/reference in the authoring container) timed on this host's
-cores on a bounded sample of the same batch and cross-checked against the GPU results.
+max-over-ranks wall time; `ms_per_step` = that wall time / --steps.
+
+A plain run does only what that line needs: set up, warm up, time the --steps steps, write the outputs
+(--dump-outputs DIR) and print the line.  Everything else runs with --full only: `kernel_ms` and
+`roofline` (HIP events around every timed launch, the in-kernel clock probe on one more step; the
+roofline prices the dominant kernel against HBM bandwidth with the algorithmic bytes of DESIGN.md),
+`cpu_baseline` (the reference's own AVX2 path, oracle/_ref, built by oracle/Makefile where the
+reference sources are present, timed on this host's cores on a bounded sample of the same batch and
+cross-checked against the GPU results), the two-in-flight, PCIe-inclusive and tl = 1000 legs and the
+secondary workloads (--no-cpu / --no-extra / --no-secondary leave parts of that out).
+
+--dump-outputs DIR writes what the last timed step computed, for a fixed seeded sample of the pairs
+(the inputs are seeded: the same arguments give the same inputs), as float .npy files: see dump_outputs().
 """
 import argparse
 import contextlib
@@ -421,6 +430,85 @@ def tl1000_leg(aligner, args, dev):
     return out
 
 
+DUMP_SAMPLE_PAIRS = 16384   # pairs per --dump-outputs sample (10 M pairs' outputs are 0.9 GB as int32 + bytes)
+DUMP_SAMPLE_SEED = 1234
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_sample(n, k=DUMP_SAMPLE_PAIRS):
+    """The fixed, seeded, sorted sample of k of the pair indices 0 .. n-1 that --dump-outputs writes (all of them for n <= k)."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname, bt, gathered, n_total):
+    """--dump-outputs: what the last timed step gave its caller, for the pairs of dump_sample(), as float .npy files under
+    `dirname` (int32 results as float64, CIGAR bytes as float32: both exact):
+      pair_index  (k,)         the sampled pairs (indices into rank 0's batch, which starts the global workload; k <= 16384)
+      offsets     (k,)         alignment offset in the target
+      scores      (k, 6)       ScoreMax: mqe, mqe_t, max, max_t, max_q, seg_length
+      cigar_len   (k,)         CIGAR bytes written
+      status      (k,)         per-pair status (0 = ok)
+      cigars      (k, stride)  CIGAR text bytes, zero past cigar_len
+      score_max   (k2,)        the step's own result (ScoreMax.max of every pair, gathered onto rank 0 with more than one rank)
+                               at dump_sample(n_total)"""
+    os.makedirs(dirname, exist_ok=True)
+    # (fewer pairs where long CIGAR slots would take the files past DUMP_MAX_BYTES: 4 bytes per CIGAR byte, 64 per pair for the rest)
+    idx = dump_sample(bt.n, min(DUMP_SAMPLE_PAIRS, (DUMP_MAX_BYTES // 2) // (4 * bt.cigar_stride + 64)))
+    it = torch.from_numpy(idx).to(bt.offsets.device)
+    cg = bt.cigars[it].cpu().numpy()
+    ln = bt.cigar_len[it].cpu().numpy()
+    cg[np.arange(cg.shape[1])[None, :] >= np.clip(ln, 0, cg.shape[1])[:, None]] = 0
+    arrays = {
+        "pair_index": idx.astype(np.float64),
+        "offsets": bt.offsets[it].cpu().numpy().astype(np.float64),
+        "scores": bt.scores[it].cpu().numpy().astype(np.float64),
+        "cigar_len": ln.astype(np.float64),
+        "status": bt.status[it].cpu().numpy().astype(np.float64),
+        "cigars": cg.astype(np.float32),
+    }
+    if gathered is not None:
+        g_idx = torch.from_numpy(dump_sample(n_total)).to(gathered.device)
+        arrays["score_max"] = gathered[g_idx].cpu().numpy().astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES, {k: a.nbytes for k, a in arrays.items()}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def profile_launches(aligner, batch, tm, in_flight, dev):
+    """--full: (timing record for the roofline, shader clock in MHz or 0, ms of one step at a time with two in flight or None)."""
+    one_in_flight_ms = None
+    if in_flight == 2:
+        # (two grids side by side: a launch's events span the other one's tail too.  The roofline's launch duration is that of ONE more
+        # launch, untimed, with the chip to itself)
+        torch.cuda.synchronize(dev)
+        aligner.set_profiling(1)
+        for _ in range(2):  # (the second one: the first follows an idle moment of the chip)
+            batch.run(aligner, GATK_PARAMETERS, SWOverhangStrategy.SOFTCLIP)
+        torch.cuda.synchronize(dev)
+        tm = aligner.timing()
+        # ... and, for the reader of the line, what this rank's steps take ONE at a time (five of them, untimed, no gather)
+        aligner.set_profiling(0)
+        t1 = time.perf_counter()
+        for _ in range(5):
+            batch.run(aligner, GATK_PARAMETERS, SWOverhangStrategy.SOFTCLIP)
+        torch.cuda.synchronize(dev)
+        one_in_flight_ms = (time.perf_counter() - t1) / 5 * 1e3
+    # the shader clock under this load, measured inside the kernel on one extra, untimed step (profiling level 2: every wave stamps
+    # s_memtime and the 100 MHz s_memrealtime around its life): what the roofline's issue-bound fraction is computed against
+    clock_mhz = 0
+    try:
+        aligner.set_profiling(2)
+        batch.run(aligner, GATK_PARAMETERS, SWOverhangStrategy.SOFTCLIP)
+        torch.cuda.synchronize(dev)
+        clock_mhz = int(aligner.timing().clock_mhz)
+    except Exception:  # noqa: BLE001 -- no clock, no issue fraction
+        clock_mhz = 0
+    aligner.set_profiling(0)
+    return tm, clock_mhz, one_in_flight_ms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -436,6 +524,12 @@ def main():
     ap.add_argument("--workspace-gib", type=float, default=None,
                     help=f"workspace per GPU for the headline; default: {DEFAULT_WORKSPACE_GIB:.0f} GiB (the 10 M-pair batch is one launch of a persistent grid), "
                          "or what the card has free beside the batch if that is less")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: kernel_ms and the roofline (HIP events, the in-kernel "
+                         "clock probe, the committed PMC passes), the CPU baseline, the two-in-flight, PCIe-inclusive and tl=1000 legs "
+                         "and the secondary workloads (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed (a fixed seeded sample of the pairs) as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true", help="skip the host-CPU baseline leg")
     ap.add_argument("--steps-in-flight", type=int, choices=(1, 2), default=None,
                     help="2: two contexts on two streams take the steps in turn, so that the next step's grid moves into the wave slots the "
@@ -457,6 +551,8 @@ def main():
     ap.add_argument("--fasta", help="--dataset fastx: reference FASTA (first record is used)")
     ap.add_argument("--fastq", help="--dataset fastx: reads, description 'pos=<0-based window start>'")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, local_rank, world = dist.init()
     distributed = torch.distributed.is_initialized()
@@ -560,9 +656,10 @@ def main():
         step()
     torch.cuda.synchronize(dev)
     step_no[0] = 0
-    # HIP events around every kernel launch, on the streams the kernels run on (asynchronous: they are
+    # --full: HIP events around every kernel launch, on the streams the kernels run on (asynchronous: they are
     # read back after the timed region) -> the MEAN launch duration over the timed steps for the roofline
-    aligner.set_profiling(3)  # summed over the timed steps, read once afterwards
+    if args.full:
+        aligner.set_profiling(3)  # summed over the timed steps, read once afterwards
     dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
@@ -576,71 +673,23 @@ def main():
     comm = dist.describe()                         # what the COMMUNICATOR says, not the environment
 
     status_bad = int(sum(int((bt.status != 0).sum().item()) for _al, bt, _st in lanes))
-    if in_flight == 2:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, lanes[(args.steps - 1) % len(lanes)][1], gathered, n_total)
+    if args.full and in_flight == 2:
         assert torch.equal(lanes[0][1].scores, lanes[1][1].scores) and torch.equal(lanes[0][1].cigars, lanes[1][1].cigars), "the two contexts disagree"
 
-    tm = aligner.timing()  # kernel durations summed over the timed steps (HIP events recorded in the timed region)
-    if in_flight == 2:
-        # (two grids side by side: a launch's events span the other one's tail too.  The roofline's launch duration is that of ONE more
-        # launch, untimed, with the chip to itself)
-        torch.cuda.synchronize(dev)
-        aligner.set_profiling(1)
-        for _ in range(2):  # (the second one: the first follows an idle moment of the chip)
-            batch.run(aligner, GATK_PARAMETERS, SWOverhangStrategy.SOFTCLIP)
-        torch.cuda.synchronize(dev)
-        tm = aligner.timing()
-        # ... and, for the reader of the line, what this rank's steps take ONE at a time (five of them, untimed, no gather)
-        aligner.set_profiling(0)
-        t1 = time.perf_counter()
-        for _ in range(5):
-            batch.run(aligner, GATK_PARAMETERS, SWOverhangStrategy.SOFTCLIP)
-        torch.cuda.synchronize(dev)
-        one_in_flight_ms = (time.perf_counter() - t1) / 5 * 1e3
-    # the shader clock under this load, measured inside the kernel on one extra, untimed step (profiling level 2: every wave stamps
-    # s_memtime and the 100 MHz s_memrealtime around its life): what the issue-bound fraction below is computed against
+    # --full: kernel durations summed over the timed steps (HIP events recorded in the timed region); a plain run reads only the
+    # record of the last call (which fill kernel, packed or not: `dtype`)
+    tm = aligner.timing()
     clock_mhz = 0
-    try:
-        aligner.set_profiling(2)
-        batch.run(aligner, GATK_PARAMETERS, SWOverhangStrategy.SOFTCLIP)
-        torch.cuda.synchronize(dev)
-        clock_mhz = int(aligner.timing().clock_mhz)
-    except Exception:  # noqa: BLE001 -- no clock, no issue fraction
-        clock_mhz = 0
-    aligner.set_profiling(0)
-
+    if args.full:
+        tm, clock_mhz, one_in_flight_ms = profile_launches(aligner, batch, tm, in_flight, dev)
     if rank != 0:
         if distributed:
             torch.distributed.destroy_process_group()
         return
     if args.dump_scores and gathered is not None:
         np.save(args.dump_scores, gathered.cpu().numpy().astype(np.int32))
-    fill_kernel = aligner.fill_kernel_name(tm)
-    total_cells = n_total * args.tl * args.ql * args.steps
-    # (tm sums the HIP events of every launch of the timed loop: mgl_sw_ctx_set_profiling(ctx, 3))
-    launches = max(1, tm.dp_launches)
-    avg_launch_s = tm.dp_ms / 1e3 / launches
-    pairs_per_launch = n_local * (1 if in_flight == 2 else args.steps) / launches
-    spills = fill_kernel not in ("sw_dp16_lane_ck_kernel",)  # every other fill kernel writes the 4-bit traceback to HBM
-    cigar_bytes = float(batch.cigar_len.float().mean().item())
-    per_pair = algorithmic_bytes_per_pair(args.tl, args.ql, args.input == "2bit", spills, cigar_bytes)
-    achieved = pairs_per_launch * per_pair / avg_launch_s / 1e9
-    pmc, pmc_current, pmc_why = pmc_entry(args.tl, args.ql, fill_kernel)
-    tpp = pmc["hbm_bytes_per_pair"] if pmc and pmc_current else None
-    traffic = None if tpp is None else round(tpp * pairs_per_launch)  # HBM bytes per launch (PMC)
-    valu = pmc.get("valu") if pmc and pmc_current else None
-    valu_obj = None
-    if valu and not (1000 <= clock_mhz <= 3000):
-        valu_obj = {"issue_frac": None, "note": "the in-kernel clock probe returned no plausible clock: the issue-bound fraction is not computed against an assumed one",
-                    "wave_insts_per_pair": valu["wave_insts_per_pair"], "source": valu.get("source", "profiles/pmc_traffic.json (rocprofv3 --pmc)")}
-    elif valu:
-        # what actually bounds this integer kernel: VALU issue.  SIMD-cycles the committed instruction count needs at the
-        # measured per-class issue costs / SIMD-cycles available in the measured launch duration (1024 SIMDs x the measured clock)
-        clock_hz = clock_mhz * 1e6
-        need = valu["wave_insts_per_pair"] * pairs_per_launch * valu["avg_cycles_per_inst"]
-        have = avg_launch_s * clock_hz * 1024
-        valu_obj = {"issue_frac": round(need / have, 3), "wave_insts_per_pair": valu["wave_insts_per_pair"],
-                    "avg_cycles_per_inst": valu["avg_cycles_per_inst"], "lds_bank_conflict_rate": valu["lds_bank_conflict_rate"],
-                    "clock_mhz": int(clock_hz / 1e6), "clock_source": "measured in the kernel (s_memtime / s_memrealtime over every wave's life, one extra untimed step)", "source": valu.get("source", "profiles/pmc_traffic.json (rocprofv3 --pmc)")}
     if args.dataset == "synthetic":
         workload = (f"BASELINE.json configs[{1 if world == 1 else 2}]: {n_total} Illumina-style {args.ql} bp reads x {args.tl}-base "
                     f"reference windows" + (f", one seeded workload sharded contiguously over {world} GPUs ({n_local} pairs on rank 0)"
@@ -648,6 +697,7 @@ def main():
                                             f", {args.pairs} pairs per GPU (weak scaling)" if world > 1 else ""))
     else:
         workload = f"{n_total} pairs ({data_label}), {args.ql} bp reads x {args.tl}-base windows"
+    total_cells = n_total * args.tl * args.ql * args.steps
     out = {
         "metric": "GCUPS (+ aligned reads/s) for 150 bp short-read batch",
         "value": round(total_cells / elapsed / 1e9, 2),
@@ -675,43 +725,75 @@ def main():
                             "gpus_visible": torch.cuda.device_count(), "ranks_per_gpu": max(1, -(-comm["world_size"] // max(1, torch.cuda.device_count()))),
                             "per_rank_ms_per_step": {"min": round(min(per_rank_s) / args.steps * 1e3, 3), "max": round(max(per_rank_s) / args.steps * 1e3, 3),
                                                      "all": [round(x / args.steps * 1e3, 3) for x in per_rank_s]}},
-            **({"rank0_ms_per_step_one_in_flight": round(one_in_flight_ms, 3),
-                "steps_in_flight_note": "two contexts on two streams take the steps in turn: the next step's grid moves into the wave slots the last one's tail "
-                                        "leaves free; every step is a whole pass over the shard into result arrays of its own.  roofline.avg_launch_ms is that of "
-                                        "one more launch with the chip to itself (a launch's events beside another grid span that grid's tail too)"}
-               if in_flight == 2 else {}),
         },
         "reads_per_s": round(n_total * args.steps / elapsed, 1),
-        "kernel_ms": ({fill_kernel: round(tm.dp_ms / (1 if in_flight == 2 else args.steps), 3), "path_walk": "inside the fill kernel (every lane walks its own two pairs)",
-                       "launches_per_step": launches / (1 if in_flight == 2 else args.steps), "averaged_over_steps": 1 if in_flight == 2 else args.steps}
-                      if fill_kernel in ("sw_dp16_lane_kernel", "sw_dp16_lane_ck_kernel") else
-                      {fill_kernel: round(tm.dp_ms / args.steps, 3), "sw_traceback_kernel": round(tm.tb_ms / args.steps, 3),
-                       "launches_per_step": launches / args.steps, "averaged_over_steps": args.steps}),
         "cigar_overflows": status_bad,
-        "roofline": {
-            "bound": "hbm", "kernel": fill_kernel,
-            "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 5),
-            "traffic": traffic,
-            # where `traffic` and `valu` come from: the committed PMC passes, printed only when taken on the kernel sources of THIS build
-            "counters": {"file": "profiles/pmc_traffic.json", "commit": pmc.get("commit") if pmc else None, "src_hash": pmc.get("src_hash") if pmc else None,
-                         "current": bool(pmc_current), "why": pmc_why},
-            "algorithmic_bytes_per_pair": round(per_pair, 1),
-            "pairs_per_launch": round(pairs_per_launch, 1),
-            "avg_launch_ms": round(avg_launch_s * 1e3, 4),
-            "kernel_gcups": round(pairs_per_launch * args.tl * args.ql / avg_launch_s / 1e9, 2),
-            # what the counters say the kernel really moves, against the same peak (null without a PMC pass for this geometry)
-            "traffic_frac_of_peak": None if traffic is None else round(traffic / avg_launch_s / 1e9 / HBM_PEAK_GBS, 4),
-            # the figure earlier rounds' lines quoted: SURVEY 8d's per-pair bytes WITH a spilled 4-bit traceback, which this kernel does not write
-            "if_traceback_were_spilled": {"bytes_per_pair": algorithmic_bytes_per_pair(args.tl, args.ql, args.input == "2bit", True, cigar_bytes),
-                                          "frac": round(pairs_per_launch * algorithmic_bytes_per_pair(args.tl, args.ql, args.input == "2bit", True, cigar_bytes)
-                                                        / avg_launch_s / 1e9 / HBM_PEAK_GBS, 4)},
-            "note": ("integer DP: the kernel is VALU-issue bound (`valu`), the HBM fraction of SURVEY 8d's algorithmic bytes is small by construction"
-                     + ("; sw_dp16_lane_ck_kernel spills no traceback: `algorithmic_bytes_per_pair` = inputs + descriptors + results, and the rows and "
-                        "checkpoints it keeps to restart from are schedule -- they show in `traffic` (rocprofv3 PMC), not here"
-                        if fill_kernel == "sw_dp16_lane_ck_kernel" else "")),
-            "valu": valu_obj,
-        },
+    }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        if distributed:
+            torch.distributed.destroy_process_group()
+        return
+    if in_flight == 2:
+        out["config"].update({
+            "rank0_ms_per_step_one_in_flight": round(one_in_flight_ms, 3),
+            "steps_in_flight_note": "two contexts on two streams take the steps in turn: the next step's grid moves into the wave slots the last one's tail "
+                                    "leaves free; every step is a whole pass over the shard into result arrays of its own.  roofline.avg_launch_ms is that of "
+                                    "one more launch with the chip to itself (a launch's events beside another grid span that grid's tail too)"})
+    fill_kernel = aligner.fill_kernel_name(tm)
+    # (tm sums the HIP events of every launch of the timed loop: mgl_sw_ctx_set_profiling(ctx, 3))
+    launches = max(1, tm.dp_launches)
+    avg_launch_s = tm.dp_ms / 1e3 / launches
+    pairs_per_launch = n_local * (1 if in_flight == 2 else args.steps) / launches
+    spills = fill_kernel not in ("sw_dp16_lane_ck_kernel",)  # every other fill kernel writes the 4-bit traceback to HBM
+    cigar_bytes = float(batch.cigar_len.float().mean().item())
+    per_pair = algorithmic_bytes_per_pair(args.tl, args.ql, args.input == "2bit", spills, cigar_bytes)
+    achieved = pairs_per_launch * per_pair / avg_launch_s / 1e9
+    pmc, pmc_current, pmc_why = pmc_entry(args.tl, args.ql, fill_kernel)
+    tpp = pmc["hbm_bytes_per_pair"] if pmc and pmc_current else None
+    traffic = None if tpp is None else round(tpp * pairs_per_launch)  # HBM bytes per launch (PMC)
+    valu = pmc.get("valu") if pmc and pmc_current else None
+    valu_obj = None
+    if valu and not (1000 <= clock_mhz <= 3000):
+        valu_obj = {"issue_frac": None, "note": "the in-kernel clock probe returned no plausible clock: the issue-bound fraction is not computed against an assumed one",
+                    "wave_insts_per_pair": valu["wave_insts_per_pair"], "source": valu.get("source", "profiles/pmc_traffic.json (rocprofv3 --pmc)")}
+    elif valu:
+        # what actually bounds this integer kernel: VALU issue.  SIMD-cycles the committed instruction count needs at the
+        # measured per-class issue costs / SIMD-cycles available in the measured launch duration (1024 SIMDs x the measured clock)
+        clock_hz = clock_mhz * 1e6
+        need = valu["wave_insts_per_pair"] * pairs_per_launch * valu["avg_cycles_per_inst"]
+        have = avg_launch_s * clock_hz * 1024
+        valu_obj = {"issue_frac": round(need / have, 3), "wave_insts_per_pair": valu["wave_insts_per_pair"],
+                    "avg_cycles_per_inst": valu["avg_cycles_per_inst"], "lds_bank_conflict_rate": valu["lds_bank_conflict_rate"],
+                    "clock_mhz": int(clock_hz / 1e6), "clock_source": "measured in the kernel (s_memtime / s_memrealtime over every wave's life, one extra untimed step)", "source": valu.get("source", "profiles/pmc_traffic.json (rocprofv3 --pmc)")}
+    out["kernel_ms"] = ({fill_kernel: round(tm.dp_ms / (1 if in_flight == 2 else args.steps), 3), "path_walk": "inside the fill kernel (every lane walks its own two pairs)",
+                         "launches_per_step": launches / (1 if in_flight == 2 else args.steps), "averaged_over_steps": 1 if in_flight == 2 else args.steps}
+                        if fill_kernel in ("sw_dp16_lane_kernel", "sw_dp16_lane_ck_kernel") else
+                        {fill_kernel: round(tm.dp_ms / args.steps, 3), "sw_traceback_kernel": round(tm.tb_ms / args.steps, 3),
+                         "launches_per_step": launches / args.steps, "averaged_over_steps": args.steps})
+    out["roofline"] = {
+        "bound": "hbm", "kernel": fill_kernel,
+        "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBS, 5),
+        "traffic": traffic,
+        # where `traffic` and `valu` come from: the committed PMC passes, printed only when taken on the kernel sources of THIS build
+        "counters": {"file": "profiles/pmc_traffic.json", "commit": pmc.get("commit") if pmc else None, "src_hash": pmc.get("src_hash") if pmc else None,
+                     "current": bool(pmc_current), "why": pmc_why},
+        "algorithmic_bytes_per_pair": round(per_pair, 1),
+        "pairs_per_launch": round(pairs_per_launch, 1),
+        "avg_launch_ms": round(avg_launch_s * 1e3, 4),
+        "kernel_gcups": round(pairs_per_launch * args.tl * args.ql / avg_launch_s / 1e9, 2),
+        # what the counters say the kernel really moves, against the same peak (null without a PMC pass for this geometry)
+        "traffic_frac_of_peak": None if traffic is None else round(traffic / avg_launch_s / 1e9 / HBM_PEAK_GBS, 4),
+        # the figure earlier rounds' lines quoted: SURVEY 8d's per-pair bytes WITH a spilled 4-bit traceback, which this kernel does not write
+        "if_traceback_were_spilled": {"bytes_per_pair": algorithmic_bytes_per_pair(args.tl, args.ql, args.input == "2bit", True, cigar_bytes),
+                                      "frac": round(pairs_per_launch * algorithmic_bytes_per_pair(args.tl, args.ql, args.input == "2bit", True, cigar_bytes)
+                                                    / avg_launch_s / 1e9 / HBM_PEAK_GBS, 4)},
+        "note": ("integer DP: the kernel is VALU-issue bound (`valu`), the HBM fraction of SURVEY 8d's algorithmic bytes is small by construction"
+                 + ("; sw_dp16_lane_ck_kernel spills no traceback: `algorithmic_bytes_per_pair` = inputs + descriptors + results, and the rows and "
+                    "checkpoints it keeps to restart from are schedule -- they show in `traffic` (rocprofv3 PMC), not here"
+                    if fill_kernel == "sw_dp16_lane_ck_kernel" else "")),
+        "valu": valu_obj,
     }
     if world == 1 and not args.no_cpu:
         if ascii_twin is not batch:  # the CPU leg reads ASCII bases and compares with the GPU's result arrays

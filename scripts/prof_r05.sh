@@ -13,7 +13,7 @@ PM="--output-format csv"
 # ---- headline kernel, one dispatch of 2 097 152 pairs (256 x 150) and of 524 288 pairs (1000 x 150)
 for shape in "256 2097152 8" "1000 524288 24"; do
   set -- $shape; TL=$1; PAIRS=$2; WS=$3
-  B="python3 bench.py --steps 1 --warmup 0 --no-cpu --no-secondary --no-extra --workspace-gib $WS --pairs $PAIRS --tl $TL"
+  B="python3 bench.py --full --steps 1 --warmup 0 --no-cpu --no-secondary --no-extra --workspace-gib $WS --pairs $PAIRS --tl $TL"
   run lane${TL}_trace --kernel-trace --stats $PM -d $O/lane${TL}_trace -- $B
   run lane${TL}_sq  --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES $PM -d $O/lane${TL}_sq -- $B
   run lane${TL}_sq2 --pmc SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_INSTS_SALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_INSTS_LDS $PM -d $O/lane${TL}_sq2 -- $B

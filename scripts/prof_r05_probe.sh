@@ -19,7 +19,7 @@ python3 scripts/summarize_prof.py $(ls -d $O/prot_*/) > $O/protein_summary.txt 2
 for v in ck_nop2 ck_nop2_nomid; do
   MGL_SW_LIB=build/variants/lib_$v.so REPS=5 FULL_ONLY=1 timeout -k 10 200 python3 scripts/lane_probe.py 10000000 > $O/$v.time.log 2>&1
   MGL_SW_LIB=build/variants/lib_$v.so timeout -k 10 200 python3 scripts/ck_clock_probe.py 10000000 > $O/$v.clock.log 2>&1
-  B="python3 bench.py --steps 1 --warmup 0 --no-cpu --no-secondary --no-extra --workspace-gib 8 --pairs 2097152"
+  B="python3 bench.py --full --steps 1 --warmup 0 --no-cpu --no-secondary --no-extra --workspace-gib 8 --pairs 2097152"
   MGL_SW_LIB=build/variants/lib_$v.so run ${v}_write --pmc WRITE_SIZE $PM -d $O/${v}_write -- $B
   MGL_SW_LIB=build/variants/lib_$v.so run ${v}_fetch --pmc FETCH_SIZE $PM -d $O/${v}_fetch -- $B
 done

@@ -3,7 +3,7 @@
 set -o pipefail
 O=gpurun_out/${1:-r04g}; mkdir -p $O
 timeout -k 10 1100 python -m pytest tests -x -q -m gpu > $O/gpu_tests.log 2>&1; echo "gpu tests rc=$?" | tee -a $O/summary.txt; tail -3 $O/gpu_tests.log | tee -a $O/summary.txt
-timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" | tee -a $O/summary.txt
+timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" | tee -a $O/summary.txt
 python - $O <<'PY' | tee -a $O/summary.txt
 import json, sys
 try:

@@ -263,9 +263,24 @@ def suite_bam():
     return rows
 
 
+def suite_fuzz():
+    """tests/test_oracle.py::test_oracle_vs_live_reference_fuzz's 600 pairs (seed 2718; ACGT and AG alphabets, four parameter
+    sets, every strategy): the test checks the restatement against these records, and against the reference live where it is built."""
+    rng = np.random.default_rng(2718)
+    psets = [(200, -150, 260, 11), (1, -1, 1, 1), (5, -4, 10, 1), (3, -1, 4, 3)]
+    rows = []
+    for k in range(600):
+        tl, ql = int(rng.integers(1, 120)), int(rng.integers(1, 120))
+        alpha = np.frombuffer(b"ACGT" if k % 2 else b"AG", np.uint8)
+        t = alpha[rng.integers(0, len(alpha), tl)].tobytes()
+        q = alpha[rng.integers(0, len(alpha), ql)].tobytes()
+        rows.append(record("fuzz", t, q, psets[k % 4], ol.STRATEGIES[(k // 4) % 4]))
+    return rows
+
+
 SUITE_FUNCS = {"known": suite_known, "tiny": suite_tiny, "random": suite_random, "ties": suite_ties,
                "shapes": suite_shapes, "config1": suite_config1, "window": suite_window, "long": suite_long, "long2": suite_long2,
-               "long3": suite_long3, "bam": suite_bam}
+               "long3": suite_long3, "bam": suite_bam, "fuzz": suite_fuzz}
 
 
 def main():

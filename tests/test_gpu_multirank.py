@@ -25,7 +25,7 @@ def _bench(nproc, extra, tmp_path, tag, backend="gloo"):
     env = dict(os.environ, MGL_DIST_BACKEND=backend, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--pairs", str(PAIRS), "--steps", "2",
-           "--warmup", "1", "--no-secondary", "--no-extra", "--no-cpu", "--dump-scores", dump] + extra
+           "--warmup", "1", "--full", "--no-secondary", "--no-extra", "--no-cpu", "--dump-scores", dump] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -2,7 +2,6 @@
 compiled reference, and -- where oracle/_ref is present -- against the reference live."""
 import hashlib
 
-import numpy as np
 import pytest
 
 import golden_io
@@ -66,17 +65,19 @@ def test_batch_driver_threads_agree():
             assert off1[k] == g.offset and cg1[k] == g.cigar and tuple(sc1[k]) == g.score
 
 
-@pytest.mark.skipif(not ol.have_ref(), reason="oracle/_ref not built (needs /root/reference)")
 def test_oracle_vs_live_reference_fuzz():
-    rng = np.random.default_rng(2718)
-    psets = [(200, -150, 260, 11), (1, -1, 1, 1), (5, -4, 10, 1), (3, -1, 4, 3)]
-    for k in range(600):
-        tl, ql = int(rng.integers(1, 120)), int(rng.integers(1, 120))
-        alpha = np.frombuffer(b"ACGT" if k % 2 else b"AG", np.uint8)
-        t = alpha[rng.integers(0, len(alpha), tl)].tobytes()
-        q = alpha[rng.integers(0, len(alpha), ql)].tobytes()
-        p, s = psets[k % 4], ol.STRATEGIES[(k // 4) % 4]
+    """600 random pairs (seed 2718, tests/golden/make_golden.py::suite_fuzz): the restatement against the compiled reference's
+    records of them (offset, CIGAR, ScoreMax, CRC of the backtrack matrix; align_avx == the scalar path where ql >= 8), and
+    against the reference live where oracle/_ref is built."""
+    rows = golden_io.load("fuzz")
+    assert len(rows) == 600
+    live = ol.have_ref()
+    for g in rows:
+        t, q, p, s, ql = g.t, g.q, g.params, g.strategy, len(g.q)
         a = ol.oracle_align(t, q, p, s, want_btr=True)
+        check(g, a)
+        if not live:
+            continue
         b = ol.ref_full(t, q, p, s, want_btr=True)
         assert (a["offset"], a["cigar"], a["score"]) == (b["offset"], b["cigar"], b["score"])
         assert (a["btr"][1:, 1:] == b["btr"][1:, 1:]).all()
