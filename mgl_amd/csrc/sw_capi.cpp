@@ -1872,6 +1872,9 @@ int mgl_sw_align_batch_device_matrix(mgl_sw_ctx *ctx, void *stream, int64_t n, c
         cmax = std::max<int>(cmax, matrix[k]);
         cmin = std::min<int>(cmin, matrix[k]);
     }
+    // without a status array the shared-target kernel could not report a tile that breaks the promise (it would keep stale
+    // results): the flag is dropped, and with it the grouped promise it implies -- every pair goes through the general path
+    if ((flags & MGL_SW_FLAG_SHARED_TARGET) && !d_status_out) flags &= ~MGL_SW_FLAG_SHARED_TARGET;
     if (flags & MGL_SW_FLAG_SHARED_TARGET) {
         int rc = kNotTaken;
         try { // (the tiles' geometries and their order are host vectors: no C++ exception crosses the C ABI)

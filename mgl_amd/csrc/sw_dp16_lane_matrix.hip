@@ -28,7 +28,8 @@
 // (DpArgs::slot_off): whatever a slot draws later needs less.  So the workspace is the sum over the S largest tiles, not S times
 // the largest (a protein database's lengths are log-normal: 41 GB instead of 117 for 3 072 slots on the bench's), and the queue ends on
 // its shortest tiles.  A tile whose pairs do not share one target and one query length breaks the caller's promise: its pairs get
-// MGL_SW_ERR_BAD_ARG in the status array and the call's status word, nothing is computed for them (never a wrong result).
+// MGL_SW_ERR_BAD_ARG in the status array (the host takes this kernel only where the caller passed one), nothing is computed for them
+// (never a wrong result).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>

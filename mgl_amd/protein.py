@@ -95,12 +95,13 @@ class IndexedBatch:
 
 
 def run_matrix(batch, aligner, code, matrix, gap_open=11, gap_extend=1, overhang_strategy=1, stream=None, binary_cigar=False,
-               grouped=False, score_only=False, shared_target=False):
+               grouped=False, score_only=False, shared_target=False, null_status=False):
     """mgl_sw_align_batch_device_matrix on a device_batch.DeviceBatch / IndexedBatch (ASCII wire format); no sync.
     ``grouped``: every aligned block of eight pairs has one (tl, ql) (MGL_SW_FLAG_GROUPED_GEOMETRY) -- true for a
     database search laid out as pair = d * Q + q with Q a multiple of eight -- which makes the packed-int16 kernel
     eligible.  ``shared_target``: every aligned block of 128 pairs shares its target and has one query length
-    (MGL_SW_FLAG_SHARED_TARGET, DatabaseSearch below): two pairs per lane, the scores of a column out of a per-strip profile."""
+    (MGL_SW_FLAG_SHARED_TARGET, DatabaseSearch below): two pairs per lane, the scores of a column out of a per-strip profile.
+    ``null_status``: pass no status array (batch.status is left untouched; the library then ignores ``shared_target``)."""
     import torch
 
     if stream is None:
@@ -115,7 +116,7 @@ def run_matrix(batch, aligner, code, matrix, gap_open=11, gap_extend=1, overhang
         batch.q_off.data_ptr(), None if getattr(batch, "q_len", None) is None else batch.q_len.data_ptr(), batch.max_tl,
         batch.max_ql, matrix.ctypes.data, code.ctypes.data,
         int(gap_open), int(gap_extend), int(overhang_strategy), batch.offsets.data_ptr(), batch.scores.data_ptr(),
-        batch.cigars.data_ptr(), batch.cigar_stride, batch.cigar_len.data_ptr(), batch.status.data_ptr(),
+        batch.cigars.data_ptr(), batch.cigar_stride, batch.cigar_len.data_ptr(), None if null_status else batch.status.data_ptr(),
         (_lib.FLAG_BINARY_CIGAR if binary_cigar else 0) | (_lib.FLAG_GROUPED_GEOMETRY if grouped else 0) |
         (_lib.FLAG_UNIFORM_GEOMETRY if getattr(batch, "uniform", False) else 0) | (_lib.FLAG_SCORE_ONLY if score_only else 0) |
         (_lib.FLAG_SHARED_TARGET if shared_target else 0))

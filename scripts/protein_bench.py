@@ -84,7 +84,14 @@ a.set_profiling(3)   # one more pass for the kernels' own times, summed over its
 run_pass(); torch.cuda.synchronize()
 tm = a.timing()
 a.set_profiling(0)
-over = sum(int((x.status != 0).sum()) for x in batches)
+# per-pair statuses: a CIGAR longer than the stride is the one harmless code (the scores stand); anything else -- a tile refused with
+# MGL_SW_ERR_BAD_ARG -- means pairs were not computed, and no rate is printed for such a pass
+from mgl_amd import _lib
+st = np.concatenate([x.status.cpu().numpy() for x in batches])
+over = int((st == _lib.ERR_CIGAR_OVERFLOW).sum())
+bad = st[(st != _lib.OK) & (st != _lib.ERR_CIGAR_OVERFLOW)]
+if bad.size:
+    sys.exit(f"protein bench: pairs with a status other than OK or CIGAR overflow (status: pairs): {dict(zip(*(v.tolist() for v in np.unique(bad, return_counts=True))))}")
 kernels = f"sw_dp16_lane_matrix{'_score' if args.score_only else ''}_kernel (tiles of 128 pairs that share their target) + sw_dp16_matrix{'_score' if args.score_only else ''}_kernel (the rest)" if shared else ("sw_dp16_matrix_kernel" if tm.packed16 else "sw_dp_matrix_kernel")
 layout_note = ""
 if shared:
