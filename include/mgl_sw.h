@@ -33,7 +33,8 @@ extern "C" {
  * kept 101), mgl_sw_explain_sized and mgl_sw_ctx_check are new.  A caller built against another number must not pass its mgl_sw_plan to
  * mgl_sw_explain (the library writes sizeof(mgl_sw_plan) of ITS header): compare mgl_sw_version() with MGL_SW_VERSION at load time -- the
  * Python mirror does (mgl_amd/_lib.py) -- or call mgl_sw_explain_sized, which never writes beyond the size it is given. */
-#define MGL_SW_VERSION 102
+/* 103: mgl_sw_plan.diag_fold. */
+#define MGL_SW_VERSION 103
 
 /* overhang strategies: sw_common.h:22-25 (= MicrosoftSmithWaterman.java:39-56) */
 #define MGL_SW_OS_SOFTCLIP 0x01
@@ -104,6 +105,8 @@ typedef struct mgl_sw_plan {
     int64_t workspace_bytes;    /* of the context's workspace that this batch would use (per-pair bytes of a chunk + the fixed part, per half) */
     int64_t workspace_fixed_bytes; /* of those, the part that does not grow with the batch: the regions of sw_dp16_lane_ck_kernel's persistent grid, one per wave slot */
     int64_t resident_waves;     /* wave slots of that grid (0: the kernel is launched one wave or workgroup per unit of work) */
+    int32_t diag_fold;          /* the checkpointed lane kernel and the long-read strip kernel without stored flags: K of their folded diagonal
+                                   (one multiply-add forms H + match / mismatch + 2 gext in their base-code form), 0 = none for these parameters */
 } mgl_sw_plan;
 
 typedef struct mgl_sw_ctx mgl_sw_ctx; /* opaque: one GPU, its workspace and stream */

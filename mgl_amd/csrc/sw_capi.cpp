@@ -328,6 +328,7 @@ struct BatchPlan {
     int64_t lane_slots; // the checkpointed lane kernel's persistent grid: wave slots of a launch (= regions of a workspace half)
     int64_t fixed_bytes; // ... the bytes of those regions: workspace of a half that does not grow with the chunk
     bool group_regions;  // a sorted device-resident chunk sized by slots: the lane part's regions, then left_area bytes for the left-over pairs
+    DiagFold fold;       // the base-code forms of the checkpointed lane kernel and of the strip kernel without stored flags: their folded diagonal (k = 0: none)
     int64_t left_area, left_pair16, left_pair32; // ... that area (its first half: the packed kernel's pieces, its second: the int32 kernel's) and a pair's bytes in each
     int64_t chunk; // pairs per chunk (the largest, where the chunks grow and shrink)
     bool dev_sort_host; // a host batch of mixed geometries whose chunks the device sorts (hooks->bring_ahead): a short first and last chunk, two fill streams
@@ -658,6 +659,13 @@ static int plan_batch_as(mgl_sw_ctx *ctx, int64_t n, const SeqSet &tset, const S
                    : lane_group ? std::min<int64_t>(ck_chip, (chunk + 127) / 128) : 0;
     P.fixed_bytes = lane_ck ? P.lane_slots * ck_region : group_regions ? P.lane_slots * ck_region + grp_left_area : 0;
     P.group_regions = group_regions;
+    // the kernels whose base-code form folds the diagonal's constant into one multiply-add where the parameters allow it (sw_device.h:
+    // diag_fold; about a thousand candidates, microseconds).  MGL_SW_DEBUG_DIAG_FOLD=0: never (read per call: the tests compare both forms)
+    {
+        const char *const dfe = getenv("MGL_SW_DEBUG_DIAG_FOLD");
+        const bool codes_form = lane_ck || lane_group || (strip16 && strip_k > 0 && strip16_lds_bytes_codes(max_ql, strip_waves) <= 64 * 1024);
+        P.fold = codes_form && !(dfe && atoi(dfe) == 0) ? diag_fold(match, mismatch, gext) : DiagFold{0, 0, 0};
+    }
     P.left_area = group_regions ? grp_left_area : 0;
     P.left_pair16 = stride_words * 2;
     P.left_pair32 = stride32_words * 4;
@@ -870,6 +878,7 @@ int run_device(mgl_sw_ctx *ctx, hipStream_t stream, int64_t n, const SeqSet &tse
         pl.workspace_fixed_bytes = P.fixed_bytes * halves;
         pl.workspace_bytes = (per_pair * chunk + P.fixed_bytes) * halves;
         pl.resident_waves = lane_slots;
+        pl.diag_fold = pl.fill_kernel == MGL_SW_KERNEL_LANE16_CK || (strip16 && strip_k > 0) ? P.fold.k : 0;
         return MGL_SW_OK;
     }
 
@@ -1130,6 +1139,9 @@ int run_device(mgl_sw_ctx *ctx, hipStream_t stream, int64_t n, const SeqSet &tse
                 const char *const sce = getenv("MGL_SW_DEBUG_STRIP_CODES"); // (0: the byte-compare form whatever the sequences; read per call: the tests run both forms)
                 da.strip_codes = strip16 && strip_k > 0 && !(sce && atoi(sce) == 0) && strip16_lds_bytes_codes(max_ql, strip_waves) <= 64 * 1024 ? 1 : 0;
             }
+            da.fold_k = P.fold.k;
+            da.fold_bm = P.fold.bm;
+            da.fold_bx = P.fold.bx;
             da.lane_slots = 0;
             da.tile_ctr = nullptr;
             da.grid_fault = nullptr;

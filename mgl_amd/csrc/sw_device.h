@@ -85,6 +85,9 @@ struct DpArgs {
     // ends (bytes off tb; slot_off[s + 1] - slot_off[s] = what the s-th largest tile needs: every later draw needs less)
     const int32_t *tile_order;
     const int64_t *slot_off;
+    // sw_dp16_lane_ck_kernel and the strip kernels without stored flags: the folded diagonal of their base-code form (diag_fold below;
+    // fold_k = 0: none, or MGL_SW_DEBUG_DIAG_FOLD=0), which selects their *_fold twins
+    int fold_k, fold_bm, fold_bx;
 };
 
 struct TbArgs {
@@ -212,6 +215,57 @@ int64_t dp_group_bytes(int sps_cap, int rows); // carry ring + query copies of o
 int dp_lds_bytes(int sps_cap, int waves_per_block, int rows);
 int dp16_lds_bytes(int sps, int waves_per_block);
 bool dp16_range_ok(int tl, int ql, int match, int mismatch, int gopen, int gext, int strategy);
+// ---- the folded diagonal of the base-code kernels (sw_lane_cell.h, CMP_FOLD).  The packed cell forms diag = H + s with s = match + 2e or
+// mismatch + 2e, wrapping mod 2^16.  Where some K and two bytes b_m, b_x in [0, 255] have b_m K == match + 2e and b_x K == mismatch + 2e
+// (mod 2^16), the column's table holds b_m / b_x instead of 0 / 1 and diag = v_pk_mad_u16(byte, K, H): one instruction instead of a
+// multiply-add and an add.  k = 0: the parameters have no such K (about 57 % of random sets; GATK's do: K = 20138, b_m 179, b_x 192).
+struct DiagFold {
+    int k, bm, bx;
+};
+__host__ __device__ inline int ctz16(unsigned x) // x in [1, 2^16)
+{
+    int s = 0;
+    while (!(x & 1u)) x >>= 1, ++s;
+    return s;
+}
+__host__ __device__ inline unsigned inv_odd16(unsigned o) // o odd: x with o x == 1 (mod 2^16) (Newton: 3, 6, 12, 24 correct bits)
+{
+    unsigned x = o;
+    for (int i = 0; i < 3; ++i) x *= 2u - o * x;
+    return x & 0xffffu;
+}
+// the byte b in [0, 255] with b k == v (mod 2^16), or -1; k in [1, 2^16), v in [0, 2^16).  With k = 2^s k', k' odd: b k' == v / 2^s (mod 2^(16-s))
+__host__ __device__ inline int fold_byte(unsigned k, unsigned v)
+{
+    const int s = ctz16(k);
+    if (v & ((1u << s) - 1u)) return -1;
+    const unsigned b = ((v >> s) * inv_odd16(k >> s)) & ((0x10000u >> s) - 1u);
+    return b <= 255u ? (int)b : -1;
+}
+// The smallest such K for the normalised parameters, with its bytes.  A K that takes some byte b_m = 2^u o in [1, 255] to a = match + 2e
+// lies in the residue class K == (a / 2^u) o^-1 (mod 2^(16-u)): about a thousand candidates over all bytes, each checked against
+// mismatch + 2e (a = 0: every K takes byte 0 there, so the classes come from the other constant; both 0: K = 1).
+__host__ __device__ inline DiagFold diag_fold(int match, int mismatch, int gext)
+{
+    const unsigned a = (unsigned)(match + 2 * gext) & 0xffffu, x = (unsigned)(mismatch + 2 * gext) & 0xffffu;
+    const unsigned p = a ? a : x;
+    DiagFold d{0, 0, 0};
+    if (!p) return DiagFold{1, 0, 0};
+    for (unsigned b = 1; b < 256u; ++b) {
+        const int u = ctz16(b);
+        if (p & ((1u << u) - 1u)) continue;
+        const unsigned period = 0x10000u >> u;
+        for (unsigned k = ((p >> u) * inv_odd16(b >> u)) & (period - 1u); k < 0x10000u && (d.k == 0 || k < (unsigned)d.k); k += period) {
+            if (k == 0) continue;
+            const int bm = fold_byte(k, a), bx = fold_byte(k, x);
+            if (bm >= 0 && bx >= 0) {
+                d = DiagFold{(int)k, bm, bx};
+                break;
+            }
+        }
+    }
+    return d;
+}
 hipError_t launch_dp16(const DpArgs &a, int waves_per_block, hipStream_t stream);
 bool lane16_supported(const SeqSet &t, const SeqSet &q);    // sw_dp16_lane_kernel (every flag stored): ASCII
 bool lane16_ck_supported(const SeqSet &t, const SeqSet &q); // sw_dp16_lane_ck_kernel: ASCII, or both sequence sets 2-bit packed

@@ -407,7 +407,7 @@ struct PathWalk {
 };
 
 // ---- pass 1: strip k, score only, keeping the rows and the column checkpoints
-template <bool LAST, bool CODES>
+template <bool LAST, int CODES>
 __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql, const int nb, const WaveMem &wm, const unsigned *qst, const unsigned *tst,
                                          const LaneConsts &c, const int gopen, const int gext, const int base, const bool indel, int &bestA,
                                          int &bestA_i, int &bestB, int &bestB_i)
@@ -442,7 +442,7 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
         unsigned e = top.y;
         uint2 mid;
         if (CODES)
-            column<R, true, true, true>(h, f, t, code_table((qa >> (8 * u)) & 0xffu), hd, e, c, nullptr, &mid, code_table((qb >> (8 * u)) & 0xffu));
+            column<R, true, true, CODES>(h, f, t, code_table((qa >> (8 * u)) & 0xffu, c.bm, c.bx), hd, e, c, nullptr, &mid, code_table((qb >> (8 * u)) & 0xffu, c.bm, c.bx));
         else
             column<R, true, true, false>(h, f, t, __builtin_amdgcn_perm(qb, qa, 0x0c040c00u + 0x00010001u * u), hd, e, c, nullptr, &mid);
         hd = top.x;
@@ -521,7 +521,7 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
 // ---- pass 2: recompute the flags of block (sA, bA) for the low halves and of block (sB, bB) for the high halves; s = 16-row band
 // (strip s / 2, its upper or lower half), b = block of CK columns.  needA / needB: the pair's walk waits for this block (a pair
 // that does not fetches nothing; its half computes garbage nobody reads).
-template <bool CODES>
+template <int CODES>
 __device__ __forceinline__ void ck_block(const int sA, const int bA, const int sB, const int bB, const bool needA, const bool needB, const BlockGeom &g,
                                          const WaveMem &wm, const LaneConsts &c, const int groups = CK / 8)
 {
@@ -611,8 +611,8 @@ __device__ __forceinline__ void ck_block(const int sA, const int bA, const int s
             unsigned e = lo_hi(va[u].y, vb[u].y);
             uint4 *const out = wm.blk + (size_t)(8 * gg + u) * 64;
             if (CODES)
-                column<RB, false, false, true>(h, f, t, code_table((qa[u >> 2] >> (8 * (u & 3))) & 0xffu), hd, e, c, out, nullptr,
-                                               code_table((qb[u >> 2] >> (8 * (u & 3))) & 0xffu));
+                column<RB, false, false, CODES>(h, f, t, code_table((qa[u >> 2] >> (8 * (u & 3))) & 0xffu, c.bm, c.bx), hd, e, c, out, nullptr,
+                                                code_table((qb[u >> 2] >> (8 * (u & 3))) & 0xffu, c.bm, c.bx));
             else
                 column<RB, false, false, false>(h, f, t, __builtin_amdgcn_perm(qb[u >> 2], qa[u >> 2], 0x0c040c00u + 0x00010001u * (u & 3)), hd, e, c, out);
             hd = lo_hi(va[u].x, vb[u].x);
@@ -749,7 +749,7 @@ __device__ __forceinline__ void lds_to_global(void *dst, const unsigned char *sr
 // none inside pass 1's loops.  Making slot and lane opaque per tile recomputes them instead and empties the scratch area by a third,
 // but the kernel ran 2.5 ms per 10 M pairs SLOWER (65.2 against 62.6: the opaque lane number hides its range from the address
 // arithmetic of every store of pass 1) -- measured, scripts/ck_regs_probe.sh, and left alone.)
-template <bool VIA_LDS>
+template <bool VIA_LDS, bool FOLD>
 __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbArgs &walk_in, const int64_t gw, const int64_t slot, const int lane, unsigned char *out_lds)
 {
     const int64_t n_ls = (a.count + 1) >> 1;
@@ -782,6 +782,11 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
         c.k34[u] = 0x01010101u << (2 * u);
         asm volatile("" : "+s"(c.k12[u]), "+s"(c.k34[u]));
     }
+    c.kf = pack2(a.fold_k, a.fold_k);
+    c.bm = FOLD ? (unsigned)a.fold_bm : 0u;
+    c.bx = FOLD ? (unsigned)a.fold_bx : 1u;
+    if (FOLD) asm volatile("" : "+s"(c.kf)); // (the bytes only build the tables: left to the compiler, four registers fewer spilled)
+    constexpr int CM = FOLD ? CMP_FOLD : CMP_CODES; // (waves whose targets are not all ACGT take the byte compare either way)
 
     const int strips = lane_strips(tl, R), nb = lane_ck_blocks(ql);
     // the wave's scratch: both queries and both targets of every lane transposed to [4-base block][A | B][lane] dwords
@@ -840,11 +845,11 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
     // ---- pass 1
     int bestA = NEG_INF, bestA_i = -1, bestB = NEG_INF, bestB_i = -1;
     if (codes) {
-        for (int k = 0; k < strips - 1; ++k) ck_strip<false, true>(k, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i);
-        ck_strip<true, true>(strips - 1, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i);
+        for (int k = 0; k < strips - 1; ++k) ck_strip<false, CM>(k, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i);
+        ck_strip<true, CM>(strips - 1, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i);
     } else {
-        for (int k = 0; k < strips - 1; ++k) ck_strip<false, false>(k, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i);
-        ck_strip<true, false>(strips - 1, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i);
+        for (int k = 0; k < strips - 1; ++k) ck_strip<false, CMP_BYTES>(k, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i);
+        ck_strip<true, CMP_BYTES>(strips - 1, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i);
     }
 
     CK_PHASE(1); // pass 1
@@ -954,9 +959,9 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
         for (int m = 32; m >= 1; m >>= 1) reach = max(reach, __shfl_xor(reach, m));
         const int groups = __builtin_amdgcn_readfirstlane((reach + 7) >> 3); // (61.80 ms per 10 M pairs against 61.98 with every block in full)
         if (codes)
-            ck_block<true>(kA, bA, kB, bB, !wa.done, !wb.done, geom, wm, c, groups);
+            ck_block<CM>(kA, bA, kB, bB, !wa.done, !wb.done, geom, wm, c, groups);
         else
-            ck_block<false>(kA, bA, kB, bB, !wa.done, !wb.done, geom, wm, c, groups);
+            ck_block<CMP_BYTES>(kA, bA, kB, bB, !wa.done, !wb.done, geom, wm, c, groups);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the block's flags are in memory
         CK_PHASE(4); // a block's flags
 #ifdef MGL_CK_PHASES
@@ -1020,7 +1025,7 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
 // 1.25 M-pair launch moved between 8.9 and 9.6 ms either way, box by box) and are gone.
 // TWO kernels, one per way the results leave (VIA_LDS: in whole lines out of LDS, TbArgs::coalesced_out; else lane by lane through the
 // caller's pointers): one kernel holding both tile functions had the registers of both to colour at once (192 spilled against 66).
-template <bool VIA_LDS>
+template <bool VIA_LDS, bool FOLD>
 __device__ __forceinline__ void lane_ck_grid(const DpArgs &a, const TbArgs &walk, unsigned char *out_lds)
 {
     const int lane = threadIdx.x & 63;
@@ -1103,7 +1108,7 @@ __device__ __forceinline__ void lane_ck_grid(const DpArgs &a, const TbArgs &walk
 #ifdef MGL_CK_TRACE
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
 #endif
-        sw_dp16_lane_ck_tile<VIA_LDS>(a, walk, tile, slot, lane, out_lds);
+        sw_dp16_lane_ck_tile<VIA_LDS, FOLD>(a, walk, tile, slot, lane, out_lds);
 #ifdef MGL_CK_TRACE
         if (lane == 0 && tile < (1 << 17)) {
             unsigned hw;
@@ -1157,11 +1162,20 @@ __device__ __forceinline__ void lane_ck_grid(const DpArgs &a, const TbArgs &walk
 __global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_kernel(const DpArgs a, const TbArgs walk)
 {
     __shared__ __attribute__((aligned(16))) unsigned char out_lds[LANE_CK_OUT_LDS_BYTES]; // a tile's results on their way out
-    lane_ck_grid<true>(a, walk, out_lds);
+    lane_ck_grid<true, false>(a, walk, out_lds);
 }
 
 // results lane by lane through the caller's pointers (scattered destinations, strides the LDS form does not take); no LDS
-__global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_scatter_kernel(const DpArgs a, const TbArgs walk) { lane_ck_grid<false>(a, walk, nullptr); }
+__global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_scatter_kernel(const DpArgs a, const TbArgs walk) { lane_ck_grid<false, false>(a, walk, nullptr); }
+
+// ... the twins for parameters with a folded diagonal (a.fold_k != 0, sw_device.h: diag_fold): the base-code waves form the diagonal
+// in one v_pk_mad_u16 (sw_lane_cell.h, CMP_FOLD)
+__global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_kernel_fold(const DpArgs a, const TbArgs walk)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char out_lds[LANE_CK_OUT_LDS_BYTES];
+    lane_ck_grid<true, true>(a, walk, out_lds);
+}
+__global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_scatter_kernel_fold(const DpArgs a, const TbArgs walk) { lane_ck_grid<false, true>(a, walk, nullptr); }
 
 // either wire format, the same for both sequence sets (the kernel stages base codes, sw_lane_cell.h)
 bool lane16_ck_supported(const SeqSet &t, const SeqSet &q) { return (t.packed2 != 0) == (q.packed2 != 0); }
@@ -1177,9 +1191,9 @@ hipError_t launch_dp16_lane_ck(const DpArgs &a, const TbArgs &walk, hipStream_t 
     if (a.lane_slots < 1 || (tiles > a.lane_slots && !a.tile_ctr)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(tiles < a.lane_slots ? tiles : a.lane_slots)), block(64);
     if (walk.coalesced_out)
-        hipLaunchKernelGGL(sw_dp16_lane_ck_kernel, grid, block, 0, stream, a, walk);
+        hipLaunchKernelGGL(a.fold_k ? sw_dp16_lane_ck_kernel_fold : sw_dp16_lane_ck_kernel, grid, block, 0, stream, a, walk);
     else
-        hipLaunchKernelGGL(sw_dp16_lane_ck_scatter_kernel, grid, block, 0, stream, a, walk);
+        hipLaunchKernelGGL(a.fold_k ? sw_dp16_lane_ck_scatter_kernel_fold : sw_dp16_lane_ck_scatter_kernel, grid, block, 0, stream, a, walk);
     return hipGetLastError();
 }
 

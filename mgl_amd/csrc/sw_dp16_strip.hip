@@ -59,10 +59,11 @@ __device__ __forceinline__ unsigned dpp_wave_shr1(unsigned lane0_value, unsigned
 // its code's byte out of the column's table) where the byte compare takes a xor and a min -- 8 instead of 9 instructions per two cells.
 // The tables (one dword per query column: byte c = 0 where the query base has code c, else 1; all ones for a query byte outside the
 // target's alphabet) are built once per pair in LDS, where the byte form keeps the query itself: four times the bytes, and no
-// instruction in the step -- each half reads its four columns' tables with one ds_read_b128.
+// instruction in the step -- each half reads its four columns' tables with one ds_read_b128.  CODES = CMP_FOLD (the *_ck_fold kernels,
+// DpArgs::fold_k != 0): the tables hold the bytes of diag_fold and the diagonal is one multiply-add (sw_lane_cell.h) -- 7 instead of 8.
 typedef int strip_int4 __attribute__((ext_vector_type(4)));
 
-template <int SR, bool NOTB, bool CODES>
+template <int SR, bool NOTB, int CODES>
 __device__ __forceinline__ void sw_dp16_strip_body(const DpArgs &a, unsigned char *smem)
 {
     const int L = threadIdx.x & 63;
@@ -78,6 +79,7 @@ __device__ __forceinline__ void sw_dp16_strip_body(const DpArgs &a, unsigned cha
     const int steps_cap = strip16_steps(a.uni_ql, W); // what the regions are sized for
     const int match = a.match, gopen = a.gopen, gext = a.gext;
     const bool indel = (a.strategy & (OS_INDEL | OS_LEAD_ID)) != 0;
+    const unsigned tab_m = CODES == CMP_FOLD ? (unsigned)a.fold_bm : 0u, tab_x = CODES == CMP_FOLD ? (unsigned)a.fold_bx : 1u; // the tables' two bytes
 
     // LDS: query as dwords (group cg = bases 4cg+1 .. 4cg+4, zero padded) | mailbox[2][W][8] | last-column key (u64) | scan results
     const int qwords = CODES ? strip16_table_words(a.uni_ql) : strip16_qwords(a.uni_ql);
@@ -105,7 +107,7 @@ __device__ __forceinline__ void sw_dp16_strip_body(const DpArgs &a, unsigned cha
                         q8 = (diff & 0xffu) ? 32u : 8u * (code & 3u);
                     }
                 }
-                Q[x] = code_table(q8);
+                Q[x] = code_table(q8, tab_m, tab_x);
             }
         } else {
             for (int x = threadIdx.x; x < qwords; x += blockDim.x) Q[x] = 0u;
@@ -128,6 +130,10 @@ __device__ __forceinline__ void sw_dp16_strip_body(const DpArgs &a, unsigned cha
         c.k34[u] = 0x01010101u << (2 * u);
         asm volatile("" : "+s"(c.k12[u]), "+s"(c.k34[u]));
     }
+    c.kf = pack2(a.fold_k, a.fold_k);
+    c.bm = tab_m;
+    c.bx = tab_x;
+    if (CODES == CMP_FOLD) asm volatile("" : "+s"(c.kf));
     const unsigned level = pack2(STRIP_LEVEL, STRIP_LEVEL);
 
     // Targets beyond the 2 NL strips of 32 rows the workgroup's lanes hold (16 384 rows with four waves) take several PASSES (round 4;
@@ -282,7 +288,7 @@ __device__ __forceinline__ void sw_dp16_strip_body(const DpArgs &a, unsigned cha
                 e = pk_sub(e, bres);
                 if (CODES) {
                     const unsigned qA = u == 0 ? tabA.x : u == 1 ? tabA.y : u == 2 ? tabA.z : tabA.w, qB = u == 0 ? tabB.x : u == 1 ? tabB.y : u == 2 ? tabB.z : tabB.w;
-                    column<SR, NOTB, false, true>(h, f, t, qA, hd, e, c, tbp + (size_t)u * 2 * 64, nullptr, qB);
+                    column<SR, NOTB, false, CODES>(h, f, t, qA, hd, e, c, tbp + (size_t)u * 2 * 64, nullptr, qB);
                 } else {
                     const unsigned q = __builtin_amdgcn_perm(qb, qa, qsel + 0x00010001u * (unsigned)u);
                     column<SR, NOTB>(h, f, t, q, hd, e, c, tbp + (size_t)u * 2 * 64);
@@ -489,15 +495,23 @@ __device__ __forceinline__ bool strip_target_is_acgt(const DpArgs &a)
     __global__ __launch_bounds__(256, MGL_STRIP_OCC(ROWS)) void NAME(const DpArgs a)     \
     {                                                                                    \
         extern __shared__ __attribute__((aligned(16))) unsigned char smem[];             \
-        sw_dp16_strip_body<ROWS, false, false>(a, smem);                                 \
+        sw_dp16_strip_body<ROWS, false, CMP_BYTES>(a, smem);                             \
     }                                                                                    \
     __global__ __launch_bounds__(256, MGL_STRIP_OCC(ROWS)) void NAME##_ck(const DpArgs a) \
     {                                                                                    \
         extern __shared__ __attribute__((aligned(16))) unsigned char smem[];             \
         if (a.strip_codes && strip_target_is_acgt(a))                                    \
-            sw_dp16_strip_body<ROWS, true, true>(a, smem);                               \
+            sw_dp16_strip_body<ROWS, true, CMP_CODES>(a, smem);                          \
         else                                                                             \
-            sw_dp16_strip_body<ROWS, true, false>(a, smem);                              \
+            sw_dp16_strip_body<ROWS, true, CMP_BYTES>(a, smem);                          \
+    }                                                                                    \
+    __global__ __launch_bounds__(256, MGL_STRIP_OCC(ROWS)) void NAME##_ck_fold(const DpArgs a) \
+    {                                                                                    \
+        extern __shared__ __attribute__((aligned(16))) unsigned char smem[];             \
+        if (a.strip_codes && strip_target_is_acgt(a))                                    \
+            sw_dp16_strip_body<ROWS, true, CMP_FOLD>(a, smem);                           \
+        else                                                                             \
+            sw_dp16_strip_body<ROWS, true, CMP_BYTES>(a, smem);                          \
     }
 MGL_STRIP_KERNEL(sw_dp16_strip_kernel, 32)
 MGL_STRIP_KERNEL(sw_dp16_strip_kernel_r31, 31)
@@ -544,9 +558,13 @@ hipError_t launch_dp16_strip(const DpArgs &a, int waves, int rows, hipStream_t s
                                                        sw_dp16_strip_kernel_r24_ck, sw_dp16_strip_kernel_r25_ck, sw_dp16_strip_kernel_r26_ck, sw_dp16_strip_kernel_r27_ck,
                                                        sw_dp16_strip_kernel_r28_ck, sw_dp16_strip_kernel_r29_ck, sw_dp16_strip_kernel_r30_ck, sw_dp16_strip_kernel_r31_ck,
                                                        sw_dp16_strip_kernel_ck};
+    static void (*const table_ck_fold[16])(const DpArgs) = {sw_dp16_strip_kernel_r17_ck_fold, sw_dp16_strip_kernel_r18_ck_fold, sw_dp16_strip_kernel_r19_ck_fold, sw_dp16_strip_kernel_r20_ck_fold,
+                                                            sw_dp16_strip_kernel_r21_ck_fold, sw_dp16_strip_kernel_r22_ck_fold, sw_dp16_strip_kernel_r23_ck_fold, sw_dp16_strip_kernel_r24_ck_fold,
+                                                            sw_dp16_strip_kernel_r25_ck_fold, sw_dp16_strip_kernel_r26_ck_fold, sw_dp16_strip_kernel_r27_ck_fold, sw_dp16_strip_kernel_r28_ck_fold,
+                                                            sw_dp16_strip_kernel_r29_ck_fold, sw_dp16_strip_kernel_r30_ck_fold, sw_dp16_strip_kernel_r31_ck_fold, sw_dp16_strip_kernel_ck_fold};
     if (rows < 17 || rows > 32) return hipErrorInvalidValue;
     if (a.strip_k > 0 && a.strip_k != 64 / rows) return hipErrorInvalidValue; // (a constant in the kernels)
-    void (*k)(const DpArgs) = a.strip_k > 0 ? table_ck[rows - 17] : table[rows - 17];
+    void (*k)(const DpArgs) = a.strip_k > 0 ? (a.strip_codes && a.fold_k ? table_ck_fold[rows - 17] : table_ck[rows - 17]) : table[rows - 17];
     hipLaunchKernelGGL(k, dim3((unsigned)a.count), dim3(64 * waves), lds, stream, a);
     return hipGetLastError();
 }

@@ -70,8 +70,12 @@ struct SeqWords {
 // ---- base codes (sw_dp16_lane_ck.hip).  Staged targets hold one code 0 .. 3 per byte, staged queries 8 x code, or 32 for a base
 // outside the target alphabet.
 constexpr unsigned CODE_SEL = 0x0c040c00u; // a row's selector: or-ed onto {0, code B, 0, code A}
-// the column's table of one pair from its staged query byte
-__device__ __forceinline__ unsigned code_table(unsigned q8) { return 0x01010101u ^ (unsigned)(1ull << q8); }
+// the column's table of one pair from its staged query byte: byte c = bm where the query base has code c, else bx (0 / 1; CMP_FOLD: the
+// bytes of diag_fold, sw_device.h).  q8 = 32 shifts the difference out of the dword (a 64-bit shift): the all-bx table.
+__device__ __forceinline__ unsigned code_table(unsigned q8, unsigned bm = 0u, unsigned bx = 1u)
+{
+    return bx * 0x01010101u ^ (unsigned)((unsigned long long)(bm ^ bx) << q8);
+}
 // four ASCII bases -> four codes (A 0, C 1, T 2, G 3: bits 1 and 2 of the byte); `bad` collects the bytes that are not one of
 // these four upper-case letters (nonzero = such a byte exists among the dword's first `valid` bytes)
 __device__ __forceinline__ unsigned ascii_codes(unsigned w, unsigned &diff)
@@ -96,8 +100,16 @@ __device__ __forceinline__ unsigned and_or(unsigned a, unsigned k, unsigned b)
     return r;
 }
 
+// How a cell learns whether its two bases differ (column<> below)
+enum CmpMode : int {
+    CMP_BYTES = 0, // raw byte compare
+    CMP_CODES = 1, // base codes: one v_perm_b32 looks the 0 / 1 up
+    CMP_FOLD = 2,  // ... and the looked-up byte times LaneConsts::kf is the diagonal's score (sw_device.h: diag_fold)
+};
+
 struct LaneConsts {
     unsigned delta, one, o_e, k2; // packed constants (both halves equal): mismatch-match, 1, o-e, match+2e
+    unsigned kf, bm, bx;          // CMP_FOLD: K in both halves (an SGPR), the table's two bytes
     // bit masks of the four rows of a traceback dword, held in SGPRs: gfx9 VOP3 takes no literal, and with the masks as
     // literals the compiler splits every v_and_or_b32 into v_and_b32 + v_or_b32 (two instructions more per cell)
     unsigned k12[4], k34[4];
@@ -113,7 +125,9 @@ struct LaneConsts {
 //                          else 1 -- and t[r] is the ROW's selector 0x0c, 4 + code B, 0x0c, code A (0x0c selects a zero byte), so
 //                          the lookup lands m in both halves at once.  Codes 0 .. 3 are the target's alphabet; a query base outside
 //                          it has the all-ones table.  One instruction less per two cells.
-template <int R, bool NOTB, bool MID = false, bool CODES = false>
+//   folded (CMP_FOLD)      the same lookup with the tables' bytes b_m / b_x of diag_fold: v_pk_mad_u16(byte, K, H) is H + match + 2e or
+//                          H + mismatch + 2e (mod 2^16) at once, where the other forms take a multiply-add and an add: one instruction less again.
+template <int R, bool NOTB, bool MID = false, int CODES = CMP_BYTES>
 __device__ __forceinline__ void column(unsigned (&h)[R], unsigned (&f)[R], const unsigned (&t)[R], const unsigned q, unsigned hd,
                                        unsigned &e, const LaneConsts &c, uint4 *tbp, uint2 *mid = nullptr, const unsigned q2 = 0u)
 {
@@ -121,13 +135,17 @@ __device__ __forceinline__ void column(unsigned (&h)[R], unsigned (&f)[R], const
     auto differ = [&](const int r) { return CODES ? __builtin_amdgcn_perm(q2, q, t[r]) : pk_min_u(q ^ t[r], c.one); };
     // the diagonal of row r + 1 is taken from H[r][j-1] BEFORE row r overwrites it with H[r][j] (so that H stays in place,
     // no copy per row), one row ahead of the recurrence
-    unsigned dg = pk_add(hd, pk_mad(differ(0), c.delta, c.k2));
+    unsigned dg = CODES == CMP_FOLD ? pk_mad(differ(0), c.kf, hd) : pk_add(hd, pk_mad(differ(0), c.delta, c.k2));
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const unsigned diag = dg;
         if (r + 1 < R) {
-            const unsigned s = pk_mad(differ(r + 1), c.delta, c.k2); // match + 2e or mismatch + 2e
-            dg = pk_add(h[r], s);
+            if (CODES == CMP_FOLD) {
+                dg = pk_mad(differ(r + 1), c.kf, h[r]);
+            } else {
+                const unsigned s = pk_mad(differ(r + 1), c.delta, c.k2); // match + 2e or mismatch + 2e
+                dg = pk_add(h[r], s);
+            }
         }
         const unsigned fr = f[r];
         const unsigned sm = pk_max(diag, fr);
