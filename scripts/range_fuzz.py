@@ -7,26 +7,16 @@ sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import numpy as np
 import oracle_lib as ol
 from mgl_amd.smithwaterman import MicrosoftSmithWaterman
+from range_guards import dp16_largest_ql, dp16_range_ok as _range_ok
 
 
 
-def range_ok(tl, ql, match, mismatch, gopen, gext):   # mirrors dp16_range_ok
-    if match <= 0 or gopen < gext:
-        return False
-    top = match * min(tl, ql) + gext * (tl + ql)
-    low = -3 * gopen - (match - mismatch) - 2 * gext - 64
-    return 32767 - top + low >= -32768 and match - mismatch <= 30000 and gopen <= 10000 and gext <= 5000 and match + 2 * gext <= 30000
+def range_ok(tl, ql, match, mismatch, gopen, gext):   # tests/range_guards.py: the mirror of dp16_range_ok
+    return _range_ok(tl, ql, match, mismatch, gopen, gext)
 
 
 def largest_ql(tl, p):
-    lo, hi = 0, 4000
-    while lo < hi:
-        mid = (lo + hi + 1) // 2
-        if range_ok(tl, mid, *p):
-            lo = mid
-        else:
-            hi = mid - 1
-    return lo
+    return dp16_largest_ql(tl, p, cap=4000)
 
 
 def run(cases, seed, log=print):
