@@ -34,7 +34,8 @@ extern "C" {
  * mgl_sw_explain (the library writes sizeof(mgl_sw_plan) of ITS header): compare mgl_sw_version() with MGL_SW_VERSION at load time -- the
  * Python mirror does (mgl_amd/_lib.py) -- or call mgl_sw_explain_sized, which never writes beyond the size it is given. */
 /* 103: mgl_sw_plan.diag_fold. */
-#define MGL_SW_VERSION 103
+/* 104: mgl_sw_local_batch_device_matrix and mgl_sw_local_hit. */
+#define MGL_SW_VERSION 104
 
 /* overhang strategies: sw_common.h:22-25 (= MicrosoftSmithWaterman.java:39-56) */
 #define MGL_SW_OS_SOFTCLIP 0x01
@@ -86,6 +87,8 @@ typedef struct mgl_sw_timing {
 #define MGL_SW_KERNEL_LANE16_CK 7 /* sw_dp16_lane_ck_kernel: the lane kernel, checkpoints instead of stored flags */
 #define MGL_SW_KERNEL_SMALL 8     /* sw_small_kernel: small batches, one wave per pair, scores kept in LDS, fill + walk in one launch */
 #define MGL_SW_KERNEL_LANE16_MATRIX 9 /* sw_dp16_lane_matrix_kernel: substitution matrix, two pairs per lane, tiles that share their target */
+#define MGL_SW_KERNEL_LOCAL_LANE 10 /* sw_local_lane_kernel: local score pass, two pairs per lane, tiles that share their target */
+#define MGL_SW_KERNEL_LOCAL 11 /* sw_local_pair_kernel: local alignment, one wave per pair, int32, ends + begin + CIGAR */
 
 /* What the library WOULD do with a batch: the planner's decisions, without running anything (mgl_sw_explain). */
 typedef struct mgl_sw_plan {
@@ -420,6 +423,48 @@ int mgl_sw_align_batch_device_matrix(mgl_sw_ctx *ctx, void *stream, int64_t n, c
                                      const int8_t *matrix, const uint8_t *code, int gopen,
                                      int gext, int strategy, int32_t *d_offset_out, mgl_sw_score *d_score_out,
                                      char *d_cigar_out, int cigar_stride, int32_t *d_cigar_len_out,
+                                     int32_t *d_status_out, int flags);
+
+/*
+ * LOCAL Smith-Waterman with a substitution matrix (NOT a reference function, and NOT the GATK function of the entries above): the score
+ * of a protein or DNA database search, as SSEARCH, SWIPE or BWA's ksw compute it.  For i = 1..tl, j = 1..ql, s = matrix[code[t[i-1]]]
+ * [code[q[j-1]]] (row = target code, as mgl_sw_align_batch_device_matrix):
+ *     E[i][j] = max(H[i-1][j] - o, E[i-1][j] - e)    (consumes target: 'D')
+ *     F[i][j] = max(H[i][j-1] - o, F[i][j-1] - e)    (consumes query: 'I')
+ *     H[i][j] = max(0, H[i-1][j-1] + s, E[i][j], F[i][j]),   H[0][*] = H[*][0] = 0, E[0][*] = F[*][0] = -inf
+ * a gap of length k costs o + (k-1) e (gopen / gext normalised as in the other entries, each at most 2^24).  score = the largest H
+ * (0 if there is no cell); (t_end, q_end) = the smallest (i, j) holding it, i first: half-open ends.  The path is walked back from
+ * there: H == 0 stops, then the diagonal ('M'), then F, then E (DESIGN.md 2's priorities); in F / E extension wins ties.  The cell it
+ * stops in is (t_begin, q_begin): the alignment is t[t_begin:t_end] against q[q_begin:q_end], its CIGAR has M / I / D only, no clips.
+ * score == 0: all four coordinates 0, an empty CIGAR.  Checked against the textbook DP in tests/ (tests/local_textbook.py).
+ *
+ * Pair k: the d_t_len[k] bytes at d_targets + d_t_start[k] against the d_q_len[k] bytes at d_queries + d_q_start[k] (ASCII, device
+ * memory; lengths at most max_tl / max_ql, else MGL_SW_ERR_BAD_ARG for that pair).  UNLIKE the GATK entries a length of 0 is valid: such a
+ * pair is a hole, its hit is all zeros, its status 0, nothing is computed for it.  matrix (32 x 32 int8) and code (256 bytes -> 0..31)
+ * are HOST pointers, copied per call.  The work is enqueued on `stream`; the call does not synchronise, except that
+ * MGL_SW_FLAG_SHARED_TARGET on kernel A reads every tile's geometry back once (8 bytes per tile) to order the tiles.
+ * mgl_sw_ctx_get_timing's fill_kernel names the kernel that ran: MGL_SW_KERNEL_LOCAL_LANE (kernel A) or MGL_SW_KERNEL_LOCAL (kernel B).
+ * flags:
+ *   MGL_SW_FLAG_SCORE_ONLY: only d_hit_out[k].score is defined (the other four fields are written as 0); d_cigar_out and
+ *     d_cigar_len_out may be NULL.
+ *   MGL_SW_FLAG_SHARED_TARGET: a promise that every aligned block of 128 pairs has ONE target (same start, same length); query lengths
+ *     may differ inside a block.  With MGL_SW_FLAG_SCORE_ONLY, a status array and a batch inside the packed kernel's range guard
+ *     (sw_local.h local_lane_ok(): 16-bit scores, S - min(S) a byte, the target in LDS) the scores come from a kernel that gives every
+ *     lane two pairs (sw_local_lane.hip); a block that breaks the promise then gets MGL_SW_ERR_BAD_ARG in d_status_out and nothing else
+ *     written.  Everything else runs the general kernel (one wave per pair, int32, sw_local.hip), whatever the layout.
+ *   MGL_SW_FLAG_BINARY_CIGAR: BAM-style uint32 elements (len << 4 | op, M=0 I=1 D=2), cigar_len in bytes.
+ * d_status_out (optional, int32 per pair): 0, MGL_SW_ERR_CIGAR_OVERFLOW (d_cigar_len_out then holds the size needed; the hit is
+ * complete), MGL_SW_ERR_UNSUPPORTED (a pair too large for the workspace, or scores beyond 2^29), MGL_SW_ERR_BAD_ARG (see above).
+ * The call fails only on bad arguments (n < 0, a null matrix / code / sequence / hit array, a code >= 32, without
+ * MGL_SW_FLAG_SCORE_ONLY a null CIGAR array or a stride below 2 -- 4 for binary) and device errors: MGL_SW_ERR_DEVICE without a GPU.
+ */
+typedef struct mgl_sw_local_hit {
+    int32_t score, t_begin, t_end, q_begin, q_end;
+} mgl_sw_local_hit;
+int mgl_sw_local_batch_device_matrix(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets, const int64_t *d_t_start,
+                                     const int32_t *d_t_len, const uint8_t *d_queries, const int64_t *d_q_start, const int32_t *d_q_len,
+                                     int max_tl, int max_ql, const int8_t *matrix, const uint8_t *code, int gopen, int gext,
+                                     mgl_sw_local_hit *d_hit_out, char *d_cigar_out, int cigar_stride, int32_t *d_cigar_len_out,
                                      int32_t *d_status_out, int flags);
 
 /*

@@ -30,16 +30,21 @@ SYMBOLS = (
     "mgl_sw_multi_create", "mgl_sw_multi_destroy", "mgl_sw_multi_device_count", "mgl_sw_multi_ctx", "mgl_sw_multi_set_workspace",
     "mgl_sw_multi_last_error", "mgl_sw_align_batch_multi", "mgl_sw_multi_last_shards", "mgl_sw_shard_by_cells",
     "mgl_sw_align_batch_2bit", "mgl_sw_register_host_buffer", "mgl_sw_unregister_host_buffer", "mgl_sw_explain",
-    "mgl_sw_explain_sized", "mgl_sw_ctx_check",
+    "mgl_sw_explain_sized", "mgl_sw_ctx_check", "mgl_sw_local_batch_device_matrix",
 )
 # MGL_SW_VERSION of the include/mgl_sw.h this mirror was written against: the structs below (Plan, Timing) are that header's, and the
 # library writes sizeof(ITS struct) through the pointers it is given -- so a library of another version is refused at load time
-ABI_VERSION = 103
+ABI_VERSION = 104
 
 
 class Score(C.Structure):
     """mgl_sw_score == ScoreMax (sw_common.h:36-40)."""
     _fields_ = [(n, C.c_int32) for n in ("mqe", "mqe_t", "max", "max_t", "max_q", "seg_length")]
+
+
+class LocalHit(C.Structure):
+    """mgl_sw_local_hit: one pair's local alignment (score, then half-open spans in target and query)."""
+    _fields_ = [(n, C.c_int32) for n in ("score", "t_begin", "t_end", "q_begin", "q_end")]
 
 
 class Timing(C.Structure):
@@ -66,7 +71,8 @@ def explain(n, max_tl, max_ql, parameters=(200, -150, 260, 11), strategy=1, flag
     return p
 
 
-FILL_KERNEL_NAMES = ("sw_dp_kernel", "sw_dp16_kernel", "sw_dp64_kernel", "sw_dp_coop_kernel", "sw_dp16_lane_kernel", "sw_dp_coop16_kernel", "sw_dp16_strip_kernel", "sw_dp16_lane_ck_kernel", "sw_small_kernel", "sw_dp16_lane_matrix_kernel")
+FILL_KERNEL_NAMES = ("sw_dp_kernel", "sw_dp16_kernel", "sw_dp64_kernel", "sw_dp_coop_kernel", "sw_dp16_lane_kernel", "sw_dp_coop16_kernel", "sw_dp16_strip_kernel", "sw_dp16_lane_ck_kernel", "sw_small_kernel", "sw_dp16_lane_matrix_kernel",
+                     "sw_local_lane_kernel", "sw_local_pair_kernel")
 
 
 def _sources_newer():
@@ -134,6 +140,8 @@ def lib():
         C.c_int] * 5 + [vp, vp, vp, C.c_int, vp, vp, C.c_int]
     L.mgl_sw_align_batch_device_matrix.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int,
                                                    C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int]
+    L.mgl_sw_local_batch_device_matrix.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int,
+                                                  vp, vp, C.c_int, vp, vp, C.c_int]
     L.mgl_sw_backtrack_matrix.argtypes = [cp, C.c_int, cp, C.c_int] + [C.c_int] * 5 + [i32p, C.POINTER(Score)]
     L.mgl_sw_cigar_from_backtrack.argtypes = [i32p, C.c_int, C.c_int, C.c_int, C.POINTER(Score), cp, C.c_int,
                                               C.POINTER(C.c_int), C.POINTER(C.c_int)]

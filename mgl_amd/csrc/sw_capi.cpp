@@ -1478,6 +1478,108 @@ int run_shared_target(mgl_sw_ctx *ctx, hipStream_t stream, int64_t n, const SeqS
 
 } // namespace
 
+// ---- what mgl_sw_local_batch_device_matrix (sw_local.cpp, its own translation unit) needs of a context: C++ names, hidden, declared
+// again at the top of sw_local.cpp.  The caller holds ctx_mutex(ctx) around every other one.
+namespace mgl_sw_host {
+
+MGL_SW_INTERNAL std::mutex &ctx_mutex(mgl_sw_ctx *ctx) { return ctx->mu; }
+MGL_SW_INTERNAL int ctx_device(mgl_sw_ctx *ctx) { return ctx->device; }
+MGL_SW_INTERNAL int ctx_cus(mgl_sw_ctx *ctx) { return ctx->n_cus; }
+MGL_SW_INTERNAL int64_t ctx_workspace_limit(mgl_sw_ctx *ctx) { return ctx->ws_limit; }
+MGL_SW_INTERNAL int ctx_fail(mgl_sw_ctx *ctx, int status, const char *what) { return fail(ctx, status, what); }
+MGL_SW_INTERNAL int ctx_hip_fail(mgl_sw_ctx *ctx, hipError_t e, const char *where) { return hip_fail(ctx, e, where); }
+
+// the matrix and the code table into the context's device copy, through its page-locked staging buffer, on `stream` behind the
+// previous call's kernels (which read the device copy)
+MGL_SW_INTERNAL int ctx_stage_matrix(mgl_sw_ctx *ctx, hipStream_t st, const int8_t *matrix, const uint8_t *code, int8_t **d_matrix, uint8_t **d_code)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, ctx->d_matrix.reserve(MATRIX_DIM * MATRIX_DIM + 256));
+    int8_t *dm = static_cast<int8_t *>(ctx->d_matrix.p);
+    uint8_t *dc = reinterpret_cast<uint8_t *>(dm) + MATRIX_DIM * MATRIX_DIM;
+    if (!ctx->pin_matrix) {
+        HIP_TRY(ctx, hipHostMalloc(&ctx->pin_matrix, MATRIX_DIM * MATRIX_DIM + 256, hipHostMallocDefault));
+        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->matrix_copied, hipEventDisableTiming));
+    } else {
+        HIP_TRY(ctx, hipEventSynchronize(ctx->matrix_copied)); // the previous call's copy has left the staging buffer
+    }
+    if (ctx->ws_idle_set) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ws_idle, 0)); // the previous call's kernels read d_matrix
+    memcpy(ctx->pin_matrix, matrix, MATRIX_DIM * MATRIX_DIM);
+    memcpy(static_cast<char *>(ctx->pin_matrix) + MATRIX_DIM * MATRIX_DIM, code, 256);
+    HIP_TRY(ctx, hipMemcpyAsync(dm, ctx->pin_matrix, MATRIX_DIM * MATRIX_DIM + 256, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipEventRecord(ctx->matrix_copied, st));
+    *d_matrix = dm;
+    *d_code = dc;
+    return MGL_SW_OK;
+}
+
+// the workspace (at least `bytes`), on `stream` behind the previous call's kernels (ws_idle); a grid fault of an earlier call is reported
+MGL_SW_INTERNAL int ctx_borrow_workspace(mgl_sw_ctx *ctx, hipStream_t st, size_t bytes, void **ws)
+{
+    const int frc = grid_fault_check(ctx);
+    if (frc != MGL_SW_OK) return frc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->ws_idle_set) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ws_idle, 0));
+    HIP_TRY(ctx, ctx->tb[0].reserve(std::max<size_t>(bytes, 256)));
+    *ws = ctx->tb[0].p;
+    return MGL_SW_OK;
+}
+
+// the call's last kernel is enqueued on `stream`: the next call waits for it before it touches the workspace.  The timing record
+// (mgl_sw_ctx_get_timing) names the kernel and its launches (no events: the call is not profiled)
+MGL_SW_INTERNAL int ctx_return_workspace(mgl_sw_ctx *ctx, hipStream_t st, int fill_kernel, int launches)
+{
+    HIP_TRY(ctx, hipEventRecord(ctx->ws_idle, st));
+    ctx->ws_idle_set = true;
+    ctx->last_chunk_count = 0; // (no slot of this call can be expanded)
+    if (ctx->profiling != 3) {
+        ctx->timing = mgl_sw_timing{};
+        ctx->pool_used = 0;
+    }
+    ctx->timing.fill_kernel = fill_kernel;
+    ctx->timing.dp_launches += launches;
+    return MGL_SW_OK;
+}
+
+// a persistent grid's tile counter (an entry of the context's ring, zero at launch, zeroed by the grid's last wave) and the device view
+// of the sticky fault word (see grid_fault_check)
+MGL_SW_INTERNAL int ctx_tile_counter(mgl_sw_ctx *ctx, hipStream_t st, unsigned **ctr, int32_t **fault)
+{
+    if (!ctx->tile_ctr.p) {
+        HIP_TRY(ctx, ctx->tile_ctr.reserve((size_t)kTileCounters * kTileCounterWords * sizeof(unsigned)));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->tile_ctr.p, 0, (size_t)kTileCounters * kTileCounterWords * sizeof(unsigned), st));
+    }
+    if (!ctx->pin_fault) {
+        HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&ctx->pin_fault), 64, hipHostMallocDefault));
+        memset(ctx->pin_fault, 0, 64);
+    }
+    *ctr = static_cast<unsigned *>(ctx->tile_ctr.p) + (size_t)(ctx->tile_seq++ % kTileCounters) * kTileCounterWords;
+    void *fault_dev = nullptr;
+    HIP_TRY(ctx, hipHostGetDevicePointer(&fault_dev, ctx->pin_fault, 0));
+    *fault = static_cast<int32_t *>(fault_dev);
+    return MGL_SW_OK;
+}
+
+// the tiles' geometries and order: `bytes` of device memory and as much page-locked host memory (the context's; `stream` is synchronised
+// before the host buffer is replaced)
+MGL_SW_INTERNAL int ctx_tile_buffers(mgl_sw_ctx *ctx, hipStream_t st, size_t bytes, void **dev, void **host)
+{
+    HIP_TRY(ctx, ctx->d_grid.reserve(bytes));
+    if (ctx->pin_tiles_cap < bytes) {
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (ctx->pin_tiles) (void)hipHostFree(ctx->pin_tiles);
+        ctx->pin_tiles = nullptr;
+        ctx->pin_tiles_cap = 0;
+        HIP_TRY(ctx, hipHostMalloc(&ctx->pin_tiles, bytes * 2, hipHostMallocDefault));
+        ctx->pin_tiles_cap = bytes * 2;
+    }
+    *dev = ctx->d_grid.p;
+    *host = ctx->pin_tiles;
+    return MGL_SW_OK;
+}
+
+} // namespace mgl_sw_host
+
 extern "C" {
 
 int mgl_sw_version(void) { return MGL_SW_VERSION; }
@@ -1861,22 +1963,11 @@ int mgl_sw_align_batch_device_matrix(mgl_sw_ctx *ctx, void *stream, int64_t n, c
     if (!matrix || !code) return fail(ctx, MGL_SW_ERR_BAD_ARG, "mgl_sw_align_batch_device_matrix: null matrix or code table");
     for (int k = 0; k < 256; ++k)
         if (code[k] >= MATRIX_DIM) return fail(ctx, MGL_SW_ERR_BAD_ARG, "mgl_sw_align_batch_device_matrix: code >= 32");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, ctx->d_matrix.reserve(MATRIX_DIM * MATRIX_DIM + 256));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int8_t *dm = static_cast<int8_t *>(ctx->d_matrix.p);
-    uint8_t *dc = reinterpret_cast<uint8_t *>(dm) + MATRIX_DIM * MATRIX_DIM;
-    if (!ctx->pin_matrix) {
-        HIP_TRY(ctx, hipHostMalloc(&ctx->pin_matrix, MATRIX_DIM * MATRIX_DIM + 256, hipHostMallocDefault));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->matrix_copied, hipEventDisableTiming));
-    } else {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->matrix_copied)); // the previous call's copy has left the staging buffer
-    }
-    if (ctx->ws_idle_set) HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ws_idle, 0)); // the previous call's kernels read d_matrix
-    memcpy(ctx->pin_matrix, matrix, MATRIX_DIM * MATRIX_DIM);
-    memcpy(static_cast<char *>(ctx->pin_matrix) + MATRIX_DIM * MATRIX_DIM, code, 256);
-    HIP_TRY(ctx, hipMemcpyAsync(dm, ctx->pin_matrix, MATRIX_DIM * MATRIX_DIM + 256, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipEventRecord(ctx->matrix_copied, st));
+    int8_t *dm = nullptr;
+    uint8_t *dc = nullptr;
+    const int mrc = mgl_sw_host::ctx_stage_matrix(ctx, st, matrix, code, &dm, &dc);
+    if (mrc != MGL_SW_OK) return mrc;
     // with length arrays the offsets are per-pair START positions (a database sequence may serve many pairs)
     const SeqSet ts{d_targets, d_t_off, d_t_len, max_tl, 0}, qs{d_queries, d_q_off, d_q_len, max_ql, 0};
     int cmax = matrix[0], cmin = matrix[0];

@@ -202,3 +202,159 @@ class DatabaseSearch:
         if self.kind[d]:
             return self.long, r * self.Q + q
         return (self.shared, r * self.Qs + q) if q < self.Qs else (self.rest, r * self.Qr + q - self.Qs)
+
+
+# ---- local (zero-floor) Smith-Waterman: mgl_sw_local_batch_device_matrix
+def dna_matrix(match=2, mismatch=-3, n_score=None):
+    """(code uint8[256], matrix int8[32, 32]) for DNA local alignment: A C G T (either case) get codes 0..3, every other byte the code
+    of N (4); +match on the diagonal of ACGT, mismatch elsewhere, N against anything ``n_score`` (default: mismatch)."""
+    code = np.full(256, 4, np.uint8)
+    for k, ch in enumerate("ACGT"):
+        code[ord(ch)] = k
+        code[ord(ch.lower())] = k
+    m = np.full((32, 32), mismatch, np.int8)
+    for k in range(4):
+        m[k, k] = match
+    m[4, :] = m[:, 4] = mismatch if n_score is None else n_score
+    return code, m
+
+
+class LocalBatch:
+    """Outputs of run_local for an IndexedBatch-like object: hits int32 [n, 5] (score, t_begin, t_end, q_begin, q_end), cigars
+    uint8 [n, cigar_stride], cigar_len / status int32 [n] (torch CUDA tensors)."""
+
+    def __init__(self, targets, t_off, t_len, queries, q_off, q_len, max_tl, max_ql, cigar_stride=256):
+        import torch
+
+        self.targets, self.t_off, self.t_len = targets, t_off, t_len
+        self.queries, self.q_off, self.q_len = queries, q_off, q_len
+        self.n, self.max_tl, self.max_ql, self.cigar_stride = t_off.numel(), int(max_tl), int(max_ql), int(cigar_stride)
+        dev = targets.device
+        self.hits = torch.zeros((self.n, 5), dtype=torch.int32, device=dev)
+        self.cigars = torch.zeros((self.n, max(self.cigar_stride, 1)), dtype=torch.uint8, device=dev)
+        self.cigar_len = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self.status = torch.zeros(self.n, dtype=torch.int32, device=dev)
+
+    def cigar_strings(self, idx=None, binary=False):
+        cg = self.cigars if idx is None else self.cigars[idx]
+        ln = self.cigar_len if idx is None else self.cigar_len[idx]
+        cg, ln = cg.cpu().numpy(), ln.cpu().numpy()
+        if binary:
+            return [cg[k, : ln[k]].view(np.uint32) for k in range(len(ln))]
+        return [cg[k, : ln[k]].tobytes().decode() for k in range(len(ln))]
+
+
+def run_local(batch, aligner, code, matrix, gap_open=11, gap_extend=1, score_only=False, shared_target=False, stream=None,
+              binary_cigar=False):
+    """mgl_sw_local_batch_device_matrix on a LocalBatch (or anything with its fields): fills batch.hits, .cigars, .cigar_len, .status;
+    no sync.  ``shared_target``: every aligned block of 128 pairs has one target (MGL_SW_FLAG_SHARED_TARGET; query lengths may differ) --
+    with ``score_only`` such a batch takes the packed score kernel when the range guard allows."""
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream(batch.targets.device)
+    code = np.ascontiguousarray(code, dtype=np.uint8)
+    matrix = np.ascontiguousarray(matrix, dtype=np.int8)
+    assert code.shape == (256,) and matrix.shape == (32, 32)
+    flags = (_lib.FLAG_SCORE_ONLY if score_only else 0) | (_lib.FLAG_SHARED_TARGET if shared_target else 0) | (
+        _lib.FLAG_BINARY_CIGAR if binary_cigar else 0)
+    L = _lib.lib()
+    rc = L.mgl_sw_local_batch_device_matrix(
+        aligner.ctx, C.c_void_p(stream.cuda_stream), batch.n, batch.targets.data_ptr(), batch.t_off.data_ptr(), batch.t_len.data_ptr(),
+        batch.queries.data_ptr(), batch.q_off.data_ptr(), batch.q_len.data_ptr(), batch.max_tl, batch.max_ql, matrix.ctypes.data,
+        code.ctypes.data, int(gap_open), int(gap_extend), batch.hits.data_ptr(), None if score_only else batch.cigars.data_ptr(),
+        batch.cigar_stride, None if score_only else batch.cigar_len.data_ptr(), batch.status.data_ptr(), flags)
+    if rc != _lib.OK:
+        raise _lib.MglSwError(rc, L.mgl_sw_last_error(aligner.ctx).decode())
+
+
+def _top_k_keys(scores, k):
+    """scores int32 [D, Q] (torch) -> (index [Q, k], score [Q, k]): score descending, then database index ascending.  One composite
+    int64 key (score << 32 | (2^32 - 1 - d)) makes torch.topk's order total."""
+    import torch
+
+    D = scores.shape[0]
+    d = torch.arange(D, device=scores.device, dtype=torch.int64).unsqueeze(1)
+    key = (scores.to(torch.int64) << 32) | (0xFFFFFFFF - d)
+    top = torch.topk(key.t(), min(k, D), dim=1, largest=True, sorted=True).values
+    return (0xFFFFFFFF - (top & 0xFFFFFFFF)), (top >> 32)
+
+
+class LocalSearch:
+    """Q query byte strings of ANY lengths against D database sequences, local Smith-Waterman, in the layout of kernel A: a tile is one
+    database sequence against up to 128 queries (sorted by length, so a tile's queries are alike and little of the wave's sweep is
+    wasted); the longest database sequences come first; the last tile of a sequence is padded with holes (pairs of length 0).
+    pair = tile_row(d) * Qp + rank(q), Qp = Q rounded up to 128.  ``db``: uint8 residues of all database sequences, ``db_off`` int64[D + 1]."""
+
+    def __init__(self, db, db_off, queries, device, cigar_stride=512):
+        import torch
+
+        db_off = np.asarray(db_off, dtype=np.int64)
+        lens = np.diff(db_off)
+        self.D, self.Q = len(lens), len(queries)
+        self.device, self.cigar_stride = device, cigar_stride
+        qlens = np.array([len(q) for q in queries], dtype=np.int64)
+        self.q_order = np.argsort(qlens, kind="stable")        # rank -> query
+        self.Qp = (self.Q + 127) // 128 * 128
+        self.d_order = np.argsort(-lens, kind="stable")        # row -> database sequence
+        self.cells = int(lens.sum()) * int(qlens.sum())
+        qoff = np.zeros(self.Q + 1, np.int64)
+        qoff[1:] = np.cumsum(qlens)
+        qbytes = b"".join(bytes(q) for q in queries) or b"\0"
+        self.db_off, self.lens, self.qoff, self.qlens = db_off, lens, qoff, qlens
+        self.db = torch.from_numpy(np.array(db, dtype=np.uint8)).to(device)
+        self.qd = torch.from_numpy(np.frombuffer(qbytes, np.uint8).copy()).to(device)
+        D, Qp = self.D, self.Qp
+        q_start = np.zeros(Qp, np.int64)
+        q_len = np.zeros(Qp, np.int32)
+        q_start[: self.Q] = qoff[:-1][self.q_order]
+        q_len[: self.Q] = qlens[self.q_order]
+        t_start = np.repeat(db_off[:-1][self.d_order], Qp)
+        t_len = np.repeat(lens[self.d_order].astype(np.int32), Qp)
+        self.score_batch = LocalBatch(self.db, torch.from_numpy(t_start).to(device), torch.from_numpy(t_len).to(device), self.qd,
+                                      torch.from_numpy(np.tile(q_start, D)).to(device), torch.from_numpy(np.tile(q_len, D)).to(device),
+                                      int(lens.max()) if D else 0, int(qlens.max()) if self.Q else 0, 0)
+
+    def score_pass(self, aligner, code, matrix, gap_open=11, gap_extend=1, stream=None):
+        """Kernel A over every (database sequence, query): scores int32 [D, Q] in database and query order (a torch CUDA tensor)."""
+        import torch
+
+        run_local(self.score_batch, aligner, code, matrix, gap_open, gap_extend, score_only=True, shared_target=True, stream=stream)
+        s = self.score_batch.hits[:, 0].view(self.D, self.Qp)[:, : self.Q]
+        inv_d = torch.from_numpy(np.argsort(self.d_order)).to(self.device)
+        inv_q = torch.from_numpy(np.argsort(self.q_order)).to(self.device)
+        return s.index_select(0, inv_d).index_select(1, inv_q)
+
+    def top_k(self, scores, k):
+        """(database index [Q, k], score [Q, k]) -- score descending, then database index ascending."""
+        return _top_k_keys(scores, k)
+
+    def align_hits(self, aligner, code, matrix, idx, gap_open=11, gap_extend=1, stream=None):
+        """Kernel B over the K * Q hit pairs (query q against database sequences idx[q, :]): a LocalBatch, pair = q * K + r."""
+        import torch
+
+        idx_np = idx.cpu().numpy().astype(np.int64)
+        Q, K = idx_np.shape
+        qs = np.repeat(np.arange(Q), K)
+        ds = idx_np.reshape(-1)
+        dev = self.device
+        b = LocalBatch(self.db, torch.from_numpy(self.db_off[:-1][ds]).to(dev), torch.from_numpy(self.lens[ds].astype(np.int32)).to(dev), self.qd,
+                       torch.from_numpy(self.qoff[:-1][qs]).to(dev), torch.from_numpy(self.qlens[qs].astype(np.int32)).to(dev),
+                       int(self.lens[ds].max()) if len(ds) else 0, int(self.qlens.max()) if Q else 0, self.cigar_stride)
+        run_local(b, aligner, code, matrix, gap_open, gap_extend, stream=stream)
+        return b
+
+    def run(self, aligner, code, matrix, gap_open=11, gap_extend=1, top_k=10, stream=None):
+        """The search: the score pass (kernel A), the top_k database sequences of every query, their full alignments (kernel B).  Returns
+        dict(index=[Q, K] int64, score=[Q, K] int32, hits=[Q, K, 5] int32, cigars=list of Q lists of K strings, status=[Q, K])."""
+        import torch
+
+        scores = self.score_pass(aligner, code, matrix, gap_open, gap_extend, stream)
+        idx, top = self.top_k(scores, top_k)
+        b = self.align_hits(aligner, code, matrix, idx, gap_open, gap_extend, stream)
+        torch.cuda.synchronize(self.device)
+        K = idx.shape[1]
+        cig = b.cigar_strings()
+        return dict(index=idx.cpu().numpy(), score=top.cpu().numpy().astype(np.int32), hits=b.hits.cpu().numpy().reshape(self.Q, K, 5),
+                    cigars=[cig[q * K:(q + 1) * K] for q in range(self.Q)], status=b.status.cpu().numpy().reshape(self.Q, K),
+                    scores=scores)
