@@ -455,6 +455,8 @@ int mgl_sw_align_batch_device_matrix(mgl_sw_ctx *ctx, void *stream, int64_t n, c
  *   MGL_SW_FLAG_BINARY_CIGAR: BAM-style uint32 elements (len << 4 | op, M=0 I=1 D=2), cigar_len in bytes.
  * d_status_out (optional, int32 per pair): 0, MGL_SW_ERR_CIGAR_OVERFLOW (d_cigar_len_out then holds the size needed; the hit is
  * complete), MGL_SW_ERR_UNSUPPORTED (a pair too large for the workspace, or scores beyond 2^29), MGL_SW_ERR_BAD_ARG (see above).
+ * A pair that the general kernel gives MGL_SW_ERR_UNSUPPORTED or MGL_SW_ERR_BAD_ARG gets a hit of all zeros and a cigar_len of 0, and
+ * no byte of its CIGAR row is written; nor is any byte of a row at or beyond that pair's cigar_len, whatever its status.
  * The call fails only on bad arguments (n < 0, a null matrix / code / sequence / hit array, a code >= 32, without
  * MGL_SW_FLAG_SCORE_ONLY a null CIGAR array or a stride below 2 -- 4 for binary) and device errors: MGL_SW_ERR_DEVICE without a GPU.
  */

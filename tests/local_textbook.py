@@ -11,7 +11,8 @@ state H: H == 0 stops, then diagonal, then F, then E; in F / E extension wins ti
 
 local_align() is the plain form (one cell at a time); local_align_np() the same function vectorised by row (the F recurrence of a row
 is a running maximum, numpy's maximum.accumulate over H - o + k e).  Both return (score, t_begin, t_end, q_begin, q_end, cigar) with
-the CIGAR as text; the two agree on every field (tests/test_local_textbook.py)."""
+the CIGAR as text; the two agree on every field (tests/test_local_textbook.py).  local_scores_np() is the score alone for one target
+against many queries at once (a tile), pinned against local_align() in the same file."""
 import numpy as np
 
 NEG = -(1 << 40)
@@ -133,6 +134,46 @@ def local_align_np(t, q, code, matrix, gap_open, gap_extend):
     bi, bj = bi + 1, bj + 1
     i0, j0, ops = _walk(t, q, code, matrix, o, e, H, E, F, bi, bj)
     return best, i0, bi, j0, bj, cigar_text(ops)
+
+
+def local_scores_np(t, qs, code, matrix, gap_open, gap_extend):
+    """The scores of one target against many queries (a tile): int64[len(qs)].  The same recurrence as local_matrices_np, one target row
+    at a time over ALL queries at once ([len(qs), longest query]), keeping only the previous row.  A query shorter than the longest is
+    padded with a column code of its own whose score lies below any real one, and the maximum is taken over a query's own columns only
+    (a cell depends on cells above and left of it, so what padding holds never reaches a real cell).  o < e goes pair by pair through
+    local_align_np (an F-made H can open a better gap than its source: no running maximum)."""
+    o, e = abs(int(gap_open)), abs(int(gap_extend))
+    n = len(qs)
+    out = np.zeros(n, np.int64)
+    if o < e:
+        for k, q in enumerate(qs):
+            out[k] = local_align_np(t, q, code, matrix, o, e)[0]
+        return out
+    code = np.asarray(code, dtype=np.int64)
+    tl, L = len(t), max((len(q) for q in qs), default=0)
+    if n == 0 or tl == 0 or L == 0:
+        return out
+    m = np.full((32, 33), -(1 << 20), np.int64)  # column 32: the padding
+    m[:, :32] = np.asarray(matrix, dtype=np.int64)
+    tc = code[np.frombuffer(bytes(t), np.uint8)]
+    qc = np.full((n, L), 32, np.int64)
+    real = np.zeros((n, L), bool)
+    for k, q in enumerate(qs):
+        qc[k, : len(q)] = code[np.frombuffer(bytes(q), np.uint8)]
+        real[k, : len(q)] = True
+    col = np.arange(L + 1, dtype=np.int64) * e
+    H = np.zeros((n, L + 1), np.int64)
+    E = np.full((n, L), NEG, np.int64)
+    g = np.empty((n, L + 1), np.int64)
+    g[:, 0] = -o
+    for i in range(tl):
+        E = np.maximum(H[:, 1:] - o, E - e)
+        hv = np.maximum(0, np.maximum(H[:, :-1] + m[tc[i]][qc], E))
+        g[:, 1:] = hv - o + col[1:]
+        F = np.maximum.accumulate(g, axis=1)[:, :-1] - col[:-1]
+        H[:, 1:] = np.maximum(hv, F)
+        out = np.maximum(out, np.where(real, H[:, 1:], 0).max(axis=1))
+    return out
 
 
 def replay(t, q, code, matrix, gap_open, gap_extend, t_begin, q_begin, cigar):

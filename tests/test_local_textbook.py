@@ -111,6 +111,39 @@ def test_the_two_textbook_forms_agree():
                 assert lt.local_align(t, q, c, m, o, e) == lt.local_align_np(t, q, c, m, o, e), (t, q, o, e)
 
 
+def test_tile_scores_equal_the_plain_form():
+    """local_scores_np (one target, all queries of a tile at once) against local_align(): random protein, random bytes under an
+    asymmetric matrix, and tied DNA repeats; empty queries and an empty target among them; the six gap models of the test above."""
+    code, mat = _blosum()
+    rng = random.Random(6)
+    amat = np.random.default_rng(6).integers(-7, 9, size=(32, 32)).astype(np.int8)
+    acode = (np.arange(256) % 32).astype(np.uint8)
+    dcode, dmat = lt.dna_matrix(1, -1)
+    pairs = 0
+    for r in range(42):
+        if r % 3 == 0:
+            c, m = code, mat
+            t = bytes(rng.choice(AA) for _ in range(rng.randint(0, 50)))
+            qs = [bytes(rng.choice(AA) for _ in range(rng.randint(0, 50))) for _ in range(5)] + [t[rng.randint(0, 20):][:40], b"", t]
+        elif r % 3 == 1:
+            c, m = acode, amat
+            t = bytes(rng.randrange(256) for _ in range(rng.randint(1, 50)))
+            qs = [bytes(rng.randrange(256) for _ in range(rng.randint(0, 50))) for _ in range(6)] + [b"", t[::-1]]
+        else:
+            c, m = dcode, dmat
+            t = b"ACGT" * rng.randint(1, 12) + b"A" * rng.randint(0, 9)
+            qs = [b"ACGT" * rng.randint(1, 9), b"A" * rng.randint(1, 12), b"", b"GTAC" * 3 + b"N" * 14 + b"GTAC" * 3, b"ACGGT" * 4, b"T"]
+        if r == 41:
+            t = b""
+        for o, e in [(11, 1), (10, 2), (5, 5), (9, 0), (0, 0), (1, 4)]:
+            got = lt.local_scores_np(t, qs, c, m, o, e)
+            assert got.dtype == np.int64 and got.tolist() == [lt.local_align(t, q, c, m, o, e)[0] for q in qs], (t, qs, o, e)
+        pairs += len(qs)
+    assert pairs >= 250
+    assert lt.local_scores_np(b"ACGT", [], dcode, dmat, 5, 1).shape == (0,)
+    assert lt.local_scores_np(b"ACGT", [b"", b""], dcode, dmat, 5, 1).tolist() == [0, 0]
+
+
 def test_top_k_orders_ties_by_database_index():
     s = np.array([[5, 9, 9, 1, 9], [0, 0, 0, 0, 0]])
     assert lt.top_k(s, 3).tolist() == [[1, 2, 4], [0, 1, 2]]
