@@ -89,6 +89,7 @@ typedef struct mgl_sw_timing {
 #define MGL_SW_KERNEL_LANE16_MATRIX 9 /* sw_dp16_lane_matrix_kernel: substitution matrix, two pairs per lane, tiles that share their target */
 #define MGL_SW_KERNEL_LOCAL_LANE 10 /* sw_local_lane_kernel: local score pass, two pairs per lane, tiles that share their target */
 #define MGL_SW_KERNEL_LOCAL 11 /* sw_local_pair_kernel: local alignment, one wave per pair, int32, ends + begin + CIGAR */
+#define MGL_SW_KERNEL_BANDED 12 /* sw_banded_kernel: the GATK function over a diagonal band, one wave per pair, int32 */
 
 /* What the library WOULD do with a batch: the planner's decisions, without running anything (mgl_sw_explain). */
 typedef struct mgl_sw_plan {
@@ -468,6 +469,46 @@ int mgl_sw_local_batch_device_matrix(mgl_sw_ctx *ctx, void *stream, int64_t n, c
                                      int max_tl, int max_ql, const int8_t *matrix, const uint8_t *code, int gopen, int gext,
                                      mgl_sw_local_hit *d_hit_out, char *d_cigar_out, int cigar_stride, int32_t *d_cigar_len_out,
                                      int32_t *d_status_out, int flags);
+
+/*
+ * BANDED alignment (NOT a reference function: the reference has no band; opt-in, for long reads whose path stays near the main
+ * diagonal).  The function of mgl_sw_align_batch_device_indexed -- same inputs, parameters, overhang strategies and outputs -- computed
+ * over the cells of a diagonal band only.  For a pair of lengths tl, ql and the call's `band` >= 0 let
+ *     lo = min(0, ql - tl) - band,   hi = max(0, ql - tl) + band;
+ * a cell (i, j), 0 <= i <= tl, 0 <= j <= ql, border row and column included, is in the band iff lo <= j - i <= hi (so (0, 0) and
+ * (tl, ql) always are).  Only in-band interior cells are computed; any value read from an out-of-band cell (H, E entering from above,
+ * F entering from the left) is minus infinity: it loses every comparison strictly, stays minus infinity under - gext, and is replaced
+ * by the open at the first in-band cell (run length 1).  The last-column scan (mqe, mqe_t) and the last-row scan (max, max_t, max_q,
+ * seg_length) visit in-band cells only, in the full-matrix order with its tie rules; the walk starts where the full-matrix walk
+ * starts and cannot leave the band.  Defined by tests/banded_textbook.py.  Two relations tie it to the full-matrix function:
+ *   (R1) band >= max(tl, ql) covers the matrix: every output equals mgl_sw_align_batch_device_indexed's;
+ *   (R2) if every cell the full-matrix walk visits is in the band, offset and CIGAR equal the full-matrix result (the six score
+ *        fields need not: mqe may come from a cell whose own path leaves the band).
+ * Everything is enqueued on `stream`; the call does not synchronise.  flags: MGL_SW_FLAG_BINARY_CIGAR; MGL_SW_FLAG_SCORE_ONLY
+ * (d_score_out only -- it must not be NULL --, no decisions kept, d_cigar_out / d_cigar_len_out may be NULL); others are ignored.
+ * The call fails before any device work with MGL_SW_ERR_BAD_ARG on n < 0, a null sequence / start / length / offset array, band < 0,
+ * an unknown strategy, max_tl < 1 or max_ql < 1, and -- without MGL_SW_FLAG_SCORE_ONLY -- a null CIGAR array or a stride below 2 (4 for
+ * binary); with MGL_SW_ERR_DEVICE without a GPU.
+ * d_status_out (optional, int32 per pair): 0; MGL_SW_ERR_BAD_ARG for a length below 1 or above max_tl / max_ql;
+ * MGL_SW_ERR_CIGAR_OVERFLOW (d_cigar_len_out holds the size needed, the scores are complete); MGL_SW_ERR_UNSUPPORTED for a pair
+ * outside the kernel's range guard or too large for one workspace slot.  The range guard (sw_banded.h banded_range_ok(), on the
+ * normalised parameters): lengths at most 2^28, gopen and gext at most 2^24, and
+ *     max(match, |mismatch|) * min(tl, ql) + 2 gopen + gext * max(tl, ql) <= 2^29.
+ * A slot (banded_pair_bytes()) holds 8 (ql + 1) bytes, 4 (tl + ql + 4) bytes and -- four bits per swept cell --
+ * 32 ceil(tl / 64) (min(ql, hi - lo + 64) + 63) bytes; the grid has up to eight waves per CU, one slot each, as far as the context's
+ * workspace limit allows, and works a larger batch off inside the one launch.  The lengths are device data, so every slot is sized for
+ * the LARGEST pair that max_tl, max_ql and the band admit (a pair's band widens with |ql - tl|: the worst has ql near
+ * (tl + 2 band + 64) / 2), not for the pairs of the batch: max_tl = max_ql = 10 000 at band 512 reserves 27 MiB a slot -- 58 GB of the
+ * (grow-only) workspace for 2 048 waves -- where a 10 000 x 10 000 pair uses 5.7 MiB.  Under a smaller workspace limit the grid has
+ * fewer waves, nothing else changes.  Pass tight max_tl / max_ql.  A pair with a non-zero status gets offset 0, a
+ * cigar_len of 0 (except overflow), scores of 0 (except overflow) and no byte of its CIGAR row written; nor is any byte of a row at or
+ * beyond that pair's cigar_len, whatever its status.  mgl_sw_ctx_get_timing's fill_kernel: MGL_SW_KERNEL_BANDED.
+ */
+int mgl_sw_align_batch_device_banded(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets, const int64_t *d_t_start,
+                                     const int32_t *d_t_len, const uint8_t *d_queries, const int64_t *d_q_start, const int32_t *d_q_len,
+                                     int max_tl, int max_ql, int match, int mismatch, int gopen, int gext, int strategy, int band,
+                                     int32_t *d_offset_out, mgl_sw_score *d_score_out, char *d_cigar_out, int cigar_stride,
+                                     int32_t *d_cigar_len_out, int32_t *d_status_out, int flags);
 
 /*
  * Logical backtrack matrix of one pair, the reference's calculateMatrix

@@ -180,6 +180,8 @@ inline int bcktrMatrix_index(int i, int j, int n_col, int bw)
 // The band-layout backtrack matrix of sw_avx.cpp:33-34,173 for callers that hold their traceback in that form:
 // (query_length + bw - 1) * ceil(target_length / bw) * bw ints, cells outside the matrix zero (the reference leaves
 // garbage there).  Filled from the logical matrix of calculateMatrix().
+// "Banded" is the reference's word for this STRIPE layout: every cell of the matrix is computed, none is pruned.  An alignment over a
+// diagonal band (cells within a width of the main diagonal only) is mgl_sw_align_batch_device_banded in mgl_sw.h.
 inline std::vector<int> calculateMatrix_banded(const char *target, int target_length, const char *query, int query_length,
                                                swParameters parameters, int overhangStrategy, ScoreMax *ez, int bw = 8)
 {

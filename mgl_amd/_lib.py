@@ -30,7 +30,7 @@ SYMBOLS = (
     "mgl_sw_multi_create", "mgl_sw_multi_destroy", "mgl_sw_multi_device_count", "mgl_sw_multi_ctx", "mgl_sw_multi_set_workspace",
     "mgl_sw_multi_last_error", "mgl_sw_align_batch_multi", "mgl_sw_multi_last_shards", "mgl_sw_shard_by_cells",
     "mgl_sw_align_batch_2bit", "mgl_sw_register_host_buffer", "mgl_sw_unregister_host_buffer", "mgl_sw_explain",
-    "mgl_sw_explain_sized", "mgl_sw_ctx_check", "mgl_sw_local_batch_device_matrix",
+    "mgl_sw_explain_sized", "mgl_sw_ctx_check", "mgl_sw_local_batch_device_matrix", "mgl_sw_align_batch_device_banded",
 )
 # MGL_SW_VERSION of the include/mgl_sw.h this mirror was written against: the structs below (Plan, Timing) are that header's, and the
 # library writes sizeof(ITS struct) through the pointers it is given -- so a library of another version is refused at load time
@@ -72,7 +72,7 @@ def explain(n, max_tl, max_ql, parameters=(200, -150, 260, 11), strategy=1, flag
 
 
 FILL_KERNEL_NAMES = ("sw_dp_kernel", "sw_dp16_kernel", "sw_dp64_kernel", "sw_dp_coop_kernel", "sw_dp16_lane_kernel", "sw_dp_coop16_kernel", "sw_dp16_strip_kernel", "sw_dp16_lane_ck_kernel", "sw_small_kernel", "sw_dp16_lane_matrix_kernel",
-                     "sw_local_lane_kernel", "sw_local_pair_kernel")
+                     "sw_local_lane_kernel", "sw_local_pair_kernel", "sw_banded_kernel")
 
 
 def _sources_newer():
@@ -142,6 +142,8 @@ def lib():
                                                    C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_int]
     L.mgl_sw_local_batch_device_matrix.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int,
                                                   vp, vp, C.c_int, vp, vp, C.c_int]
+    L.mgl_sw_align_batch_device_banded.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int] + [C.c_int] * 6 + [
+        vp, vp, vp, C.c_int, vp, vp, C.c_int]
     L.mgl_sw_backtrack_matrix.argtypes = [cp, C.c_int, cp, C.c_int] + [C.c_int] * 5 + [i32p, C.POINTER(Score)]
     L.mgl_sw_cigar_from_backtrack.argtypes = [i32p, C.c_int, C.c_int, C.c_int, C.POINTER(Score), cp, C.c_int,
                                               C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -148,6 +148,66 @@ class MicrosoftSmithWaterman:
         _check(rc, ctx)
         return BatchResult(off, sc, CigarColumn(cg.reshape(n, cigar_stride), ln), ln)
 
+    def align_banded(self, refs, alts, band, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,
+                     binary_cigar=False, score_only=False, return_status=False):
+        """mgl_sw_align_batch_device_banded over lists of byte strings: the alignment of refs[k] against alts[k] computed over the cells
+        within ``band`` of the main diagonal only (lo = min(0, ql - tl) - band <= j - i <= max(0, ql - tl) + band).  NOT a reference
+        function: a band that holds a pair's full-matrix path gives the full-matrix offset and CIGAR, a narrower one need not.  Returns
+        what align_batch returns (with ``return_status`` the per-pair status array as well, and no exception for a pair's status)."""
+        import torch
+
+        ts, qs = [bytes(x) for x in refs], [bytes(x) for x in alts]
+        n = len(ts)
+        assert len(qs) == n
+        dev = torch.device("cuda", self._device)
+        td, toff = concat(ts)
+        qd, qoff = concat(qs)
+        g = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+        tlen, qlen = np.diff(toff).astype(np.int32), np.diff(qoff).astype(np.int32)
+        max_tl, max_ql = int(tlen.max(initial=1)), int(qlen.max(initial=1))
+        if cigar_stride is None:
+            cigar_stride = max(16, 2 * max(max_tl, max_ql)) * (4 if binary_cigar else 1)
+        out = self.align_banded_device(g(np.concatenate([td, np.zeros(8, np.uint8)])), g(toff[:-1]), g(tlen),
+                                       g(np.concatenate([qd, np.zeros(8, np.uint8)])), g(qoff[:-1]), g(qlen), max_tl, max_ql, band, parameters,
+                                       overhang_strategy, cigar_stride, binary_cigar, score_only)
+        torch.cuda.synchronize(dev)
+        off, sc, cg, ln, st = (None if x is None else x.cpu().numpy() for x in out)
+        if not return_status and st.any():
+            k = int(np.flatnonzero(st)[0])
+            raise _lib.MglSwError(int(st[k]), f"pair {k}")
+        if score_only:
+            res = BatchResult(off, sc, None, None)
+        else:
+            res = BatchResult(off, sc, CigarColumn(cg.reshape(n, cigar_stride), ln), ln)
+        return (res, st) if return_status else res
+
+    def align_banded_device(self, targets, t_start, t_len, queries, q_start, q_len, max_tl, max_ql, band, parameters=GATK_PARAMETERS,
+                            overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None, binary_cigar=False, score_only=False, out=None):
+        """The device-tensor form: torch tensors on this context's GPU (uint8 bytes, int64 starts, int32 lengths); enqueued on the current
+        stream, not synchronised.  Returns (offsets, scores[n, 6], cigar bytes[n * stride] or None, cigar lengths or None, status)
+        tensors; ``out``: such a tuple to write into."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(t_start.numel())
+        dev = targets.device
+        if cigar_stride is None:
+            cigar_stride = max(16, 2 * max(max_tl, max_ql)) * (4 if binary_cigar else 1)
+        if out is None:
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 6), dtype=torch.int32, device=dev),
+                   None if score_only else torch.empty(n * cigar_stride, dtype=torch.uint8, device=dev),
+                   None if score_only else torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+        off, sc, cg, ln, st = out
+        p = SWParameters(*parameters)
+        flags = (_lib.FLAG_BINARY_CIGAR if binary_cigar else 0) | (_lib.FLAG_SCORE_ONLY if score_only else 0)
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        rc = _lib.lib().mgl_sw_align_batch_device_banded(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len),
+            int(max_tl), int(max_ql), p.match, p.mismatch, p.gap_open, p.gap_extend, int(overhang_strategy), int(band), ptr(off), ptr(sc), ptr(cg),
+            int(cigar_stride), ptr(ln), ptr(st), flags)
+        _check(rc, ctx)
+        return out
+
     def align_packed_2bit(self, target_bases, target_base_count, t_start, t_len, query_bases, query_base_count, q_start, q_len,
                           max_tl, max_ql, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,
                           out=None):
