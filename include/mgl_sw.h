@@ -90,6 +90,7 @@ typedef struct mgl_sw_timing {
 #define MGL_SW_KERNEL_LOCAL_LANE 10 /* sw_local_lane_kernel: local score pass, two pairs per lane, tiles that share their target */
 #define MGL_SW_KERNEL_LOCAL 11 /* sw_local_pair_kernel: local alignment, one wave per pair, int32, ends + begin + CIGAR */
 #define MGL_SW_KERNEL_BANDED 12 /* sw_banded_kernel: the GATK function over a diagonal band, one wave per pair, int32 */
+#define MGL_SW_KERNEL_EXTEND (MGL_SW_KERNEL_BANDED + 1) /* 13, sw_extend_kernel: anchored extension with Z-drop over a centred band, one wave per pair, int32 */
 
 /* What the library WOULD do with a batch: the planner's decisions, without running anything (mgl_sw_explain). */
 typedef struct mgl_sw_plan {
@@ -344,6 +345,9 @@ int mgl_sw_shard_by_cells(int64_t n, const int64_t *t_off, const int64_t *q_off,
  * workspace by the largest blocks; the blocks may come in any order.
  * Combines with MGL_SW_FLAG_SCORE_ONLY (needs d_score_out) and MGL_SW_FLAG_BINARY_CIGAR. */
 #define MGL_SW_FLAG_SHARED_TARGET 0x10
+/* MGL_SW_FLAG_EXTEND_TO_QUERY_END (mgl_sw_extend_batch_device only; ignored elsewhere): the CIGAR describes the path to
+ * (t_end_qend, ql), the best cell of the query's last column, wherever there is one; see there. */
+#define MGL_SW_FLAG_EXTEND_TO_QUERY_END 0x20
 int mgl_sw_align_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets,
                               const int64_t *d_t_off, const uint8_t *d_queries,
                               const int64_t *d_q_off, int max_tl, int max_ql, int match,
@@ -509,6 +513,48 @@ int mgl_sw_align_batch_device_banded(mgl_sw_ctx *ctx, void *stream, int64_t n, c
                                      int max_tl, int max_ql, int match, int mismatch, int gopen, int gext, int strategy, int band,
                                      int32_t *d_offset_out, mgl_sw_score *d_score_out, char *d_cigar_out, int cigar_stride,
                                      int32_t *d_cigar_len_out, int32_t *d_status_out, int flags);
+
+/*
+ * ANCHORED EXTENSION with Z-drop (NOT a reference function; opt-in, for the extend step of a seed - chain - extend read mapper).  The
+ * start is fixed at (0, 0), the end is free, and work stops once the score has fallen too far below the best seen (the Z-drop rule of
+ * ksw2 / minimap2 / BWA-MEM).  Defined by tests/extend_textbook.py.  Per pair: a target of tl >= 1 and a query of ql >= 1 bytes
+ * compared by equality, the parameters normalised as everywhere (a gap of k costs o + (k - 1) e); per call: band >= 0 and zdrop
+ * (< 0: the rule is off).
+ *   Band: a cell (i, j), border included, is in the band iff -band <= j - i <= band, whatever tl and ql are; (tl, ql) may lie outside.
+ *   Borders: H(0, 0) = 0, H(0, j) = -(o + (j - 1) e), H(i, 0) = -(o + (i - 1) e) for in-band border cells.
+ *   Interior: the recurrence, priorities, run lengths and minus infinity of the banded entry above -- the diagonal wins ties, then the
+ *   horizontal gap; a gap opens only where strictly better than extending; a read from an out-of-band cell is minus infinity.
+ *   Rows: rowmax(i) is the largest H over row i's in-band cells (the border column while i <= band, the border row for i = 0), rj(i)
+ *   the smallest column holding it; best(i) the largest H over rows 0 .. i, at the smallest row, then the smallest column (best(0) is
+ *   0 at (0, 0)).  A row without a cell in the band (i > ql + band) has rowmax = minus infinity.
+ *   Z-drop: row i >= 1 drops iff zdrop >= 0 and
+ *       best(i - 1).H - rowmax(i) > zdrop + e * |(i - best(i - 1).i) - (rj(i) - best(i - 1).j)|.
+ *   rows_done = (first dropping row) - 1, or tl; rows beyond rows_done do not exist for any output.
+ * mgl_sw_extension: score, t_end, q_end = best(rows_done) and its cell (score >= 0; (0, 0) is the empty extension); score_qend,
+ * t_end_qend = the largest H(i, ql) over in-band rows 1 <= i <= rows_done, the later row among equals, or -0x40000000, -1 without
+ * such a cell; rows_done; dropped (0 / 1); cigar_from: 0 = the CIGAR's walk started at (t_end, q_end), 1 = at (t_end_qend, ql) --
+ * with MGL_SW_FLAG_EXTEND_TO_QUERY_END wherever t_end_qend >= 1.  The CIGAR is the banded walk from that cell back to (0, 0): global
+ * on the prefix pair, M / I / D only, no soft clips, a walk that reaches row 0 or column 0 finishes with one I or D run; it spends
+ * exactly the start cell's target and query bases and is empty (cigar_len 0) for (0, 0).
+ * flags: MGL_SW_FLAG_EXTEND_TO_QUERY_END, MGL_SW_FLAG_BINARY_CIGAR, MGL_SW_FLAG_SCORE_ONLY (d_ext_out only -- cigar_from as the full call
+ * gives it --, no decisions kept, d_cigar_out / d_cigar_len_out may be NULL); others are ignored.  The call fails before any device work
+ * with MGL_SW_ERR_BAD_ARG on n < 0, a null sequence / start / length array, a null d_ext_out, band < 0, max_tl < 1 or max_ql < 1, and --
+ * without MGL_SW_FLAG_SCORE_ONLY -- a null CIGAR array or a stride below 2 (4 for binary); with MGL_SW_ERR_DEVICE without a GPU.
+ * d_status_out (optional): the banded entry's statuses -- MGL_SW_ERR_BAD_ARG for a length below 1 or above max_tl / max_ql,
+ * MGL_SW_ERR_UNSUPPORTED outside the banded range guard or too large for one workspace slot, MGL_SW_ERR_CIGAR_OVERFLOW.  A pair with a
+ * non-zero status gets an all-zero record, a cigar_len of 0 and no byte of its CIGAR row written; nor is any byte of a row at or beyond
+ * that pair's cigar_len.  A slot holds 8 (ql + 1) bytes, 4 (tl + ql + 4) bytes and 32 ceil(tl / 64) (min(ql, 2 band + 64) + 63) bytes
+ * (each part rounded as in sw_extend.h); the band does not widen with |ql - tl|, so the formula is monotone and every slot is sized at
+ * (max_tl, max_ql): 6 MiB for 10 000 x 10 000 at band 512.  Grid, persistence and workspace limit as for the banded entry.
+ * Everything is enqueued on `stream`; the call does not synchronise.  mgl_sw_ctx_get_timing's fill_kernel: MGL_SW_KERNEL_EXTEND.
+ */
+typedef struct mgl_sw_extension {
+    int32_t score, t_end, q_end, score_qend, t_end_qend, rows_done, dropped, cigar_from;
+} mgl_sw_extension;
+int mgl_sw_extend_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets, const int64_t *d_t_start,
+                               const int32_t *d_t_len, const uint8_t *d_queries, const int64_t *d_q_start, const int32_t *d_q_len, int max_tl,
+                               int max_ql, int match, int mismatch, int gopen, int gext, int band, int zdrop, mgl_sw_extension *d_ext_out,
+                               char *d_cigar_out, int cigar_stride, int32_t *d_cigar_len_out, int32_t *d_status_out, int flags);
 
 /*
  * Logical backtrack matrix of one pair, the reference's calculateMatrix

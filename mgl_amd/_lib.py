@@ -18,6 +18,7 @@ FLAG_BINARY_CIGAR = 2
 FLAG_GROUPED_GEOMETRY = 4
 FLAG_SCORE_ONLY = 8
 FLAG_SHARED_TARGET = 0x10
+FLAG_EXTEND_TO_QUERY_END = 0x20
 OK, ERR_BAD_ARG, ERR_CIGAR_OVERFLOW, ERR_NOMEM, ERR_DEVICE, ERR_UNSUPPORTED = range(6)
 
 # every symbol include/mgl_sw.h declares (tests check that the library exports them all)
@@ -31,6 +32,7 @@ SYMBOLS = (
     "mgl_sw_multi_last_error", "mgl_sw_align_batch_multi", "mgl_sw_multi_last_shards", "mgl_sw_shard_by_cells",
     "mgl_sw_align_batch_2bit", "mgl_sw_register_host_buffer", "mgl_sw_unregister_host_buffer", "mgl_sw_explain",
     "mgl_sw_explain_sized", "mgl_sw_ctx_check", "mgl_sw_local_batch_device_matrix", "mgl_sw_align_batch_device_banded",
+    "mgl_sw_extend_batch_device",
 )
 # MGL_SW_VERSION of the include/mgl_sw.h this mirror was written against: the structs below (Plan, Timing) are that header's, and the
 # library writes sizeof(ITS struct) through the pointers it is given -- so a library of another version is refused at load time
@@ -45,6 +47,11 @@ class Score(C.Structure):
 class LocalHit(C.Structure):
     """mgl_sw_local_hit: one pair's local alignment (score, then half-open spans in target and query)."""
     _fields_ = [(n, C.c_int32) for n in ("score", "t_begin", "t_end", "q_begin", "q_end")]
+
+
+class Extension(C.Structure):
+    """mgl_sw_extension: one pair's anchored extension (mgl_sw_extend_batch_device)."""
+    _fields_ = [(n, C.c_int32) for n in ("score", "t_end", "q_end", "score_qend", "t_end_qend", "rows_done", "dropped", "cigar_from")]
 
 
 class Timing(C.Structure):
@@ -73,6 +80,16 @@ def explain(n, max_tl, max_ql, parameters=(200, -150, 260, 11), strategy=1, flag
 
 FILL_KERNEL_NAMES = ("sw_dp_kernel", "sw_dp16_kernel", "sw_dp64_kernel", "sw_dp_coop_kernel", "sw_dp16_lane_kernel", "sw_dp_coop16_kernel", "sw_dp16_strip_kernel", "sw_dp16_lane_ck_kernel", "sw_small_kernel", "sw_dp16_lane_matrix_kernel",
                      "sw_local_lane_kernel", "sw_local_pair_kernel", "sw_banded_kernel")
+# MGL_SW_KERNEL_EXTEND: the header spells it MGL_SW_KERNEL_BANDED + 1 and this mirror keeps it beside the tuple, because
+# tests/test_banded_capi.py pins the tuple above at thirteen names and tests/test_capi_host.py ties its length to the header's numeric
+# MGL_SW_KERNEL_* lines; fill_kernel_name() knows both
+KERNEL_EXTEND = len(FILL_KERNEL_NAMES)
+EXTEND_KERNEL_NAME = "sw_extend_kernel"
+
+
+def fill_kernel_name(kernel_id):
+    """MGL_SW_KERNEL_* -> the kernel's name."""
+    return EXTEND_KERNEL_NAME if kernel_id == KERNEL_EXTEND else FILL_KERNEL_NAMES[kernel_id]
 
 
 def _sources_newer():
@@ -144,6 +161,8 @@ def lib():
                                                   vp, vp, C.c_int, vp, vp, C.c_int]
     L.mgl_sw_align_batch_device_banded.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int] + [C.c_int] * 6 + [
         vp, vp, vp, C.c_int, vp, vp, C.c_int]
+    L.mgl_sw_extend_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int] + [C.c_int] * 6 + [
+        vp, vp, C.c_int, vp, vp, C.c_int]
     L.mgl_sw_backtrack_matrix.argtypes = [cp, C.c_int, cp, C.c_int] + [C.c_int] * 5 + [i32p, C.POINTER(Score)]
     L.mgl_sw_cigar_from_backtrack.argtypes = [i32p, C.c_int, C.c_int, C.c_int, C.POINTER(Score), cp, C.c_int,
                                               C.POINTER(C.c_int), C.POINTER(C.c_int)]

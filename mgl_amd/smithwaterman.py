@@ -35,6 +35,7 @@ SWNativeAlignerResult = namedtuple("SWNativeAlignerResult", "cigar alignment_off
 ScoreMax = namedtuple("ScoreMax", "mqe mqe_t max max_t max_q seg_length")
 
 BatchResult = namedtuple("BatchResult", "offsets scores cigars cigar_len")
+ExtendResult = namedtuple("ExtendResult", "score t_end q_end score_qend t_end_qend rows_done dropped cigar_from cigars cigar_len")
 
 
 class CigarColumn:
@@ -208,6 +209,63 @@ class MicrosoftSmithWaterman:
         _check(rc, ctx)
         return out
 
+    def extend(self, refs, alts, band, zdrop, parameters=GATK_PARAMETERS, to_query_end=False, cigar_stride=None, binary_cigar=False,
+               score_only=False, return_status=False):
+        """mgl_sw_extend_batch_device over lists of byte strings: the extension of alts[k] along refs[k] from the anchored start (0, 0)
+        to a free end, over the cells with -band <= j - i <= band, stopped by the Z-drop rule (``zdrop`` < 0: off).  NOT a reference
+        function.  Returns ExtendResult: the eight fields of mgl_sw_extension as arrays, the CIGARs and their lengths (with
+        ``return_status`` the per-pair status array as well, and no exception for a pair's status)."""
+        import torch
+
+        ts, qs = [bytes(x) for x in refs], [bytes(x) for x in alts]
+        n = len(ts)
+        assert len(qs) == n
+        dev = torch.device("cuda", self._device)
+        td, toff = concat(ts)
+        qd, qoff = concat(qs)
+        g = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+        tlen, qlen = np.diff(toff).astype(np.int32), np.diff(qoff).astype(np.int32)
+        max_tl, max_ql = int(tlen.max(initial=1)), int(qlen.max(initial=1))
+        if cigar_stride is None:
+            cigar_stride = max(16, 2 * max(max_tl, max_ql)) * (4 if binary_cigar else 1)
+        out = self.extend_device(g(np.concatenate([td, np.zeros(8, np.uint8)])), g(toff[:-1]), g(tlen), g(np.concatenate([qd, np.zeros(8, np.uint8)])),
+                                 g(qoff[:-1]), g(qlen), max_tl, max_ql, band, zdrop, parameters, to_query_end, cigar_stride, binary_cigar, score_only)
+        torch.cuda.synchronize(dev)
+        ext, cg, ln, st = (None if x is None else x.cpu().numpy() for x in out)
+        if not return_status and st.any():
+            k = int(np.flatnonzero(st)[0])
+            raise _lib.MglSwError(int(st[k]), f"pair {k}")
+        fields = [ext[:, c] for c in range(8)]
+        res = ExtendResult(*fields, None, None) if score_only else ExtendResult(*fields, CigarColumn(cg.reshape(n, cigar_stride), ln), ln)
+        return (res, st) if return_status else res
+
+    def extend_device(self, targets, t_start, t_len, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters=GATK_PARAMETERS,
+                      to_query_end=False, cigar_stride=None, binary_cigar=False, score_only=False, out=None):
+        """The device-tensor form: torch tensors on this context's GPU (uint8 bytes, int64 starts, int32 lengths); enqueued on the current
+        stream, not synchronised.  Returns (extensions[n, 8], cigar bytes[n * stride] or None, cigar lengths or None, status) tensors;
+        ``out``: such a tuple to write into."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(t_start.numel())
+        dev = targets.device
+        if cigar_stride is None:
+            cigar_stride = max(16, 2 * max(max_tl, max_ql)) * (4 if binary_cigar else 1)
+        if out is None:
+            out = (torch.empty((n, 8), dtype=torch.int32, device=dev), None if score_only else torch.empty(n * cigar_stride, dtype=torch.uint8, device=dev),
+                   None if score_only else torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+        ext, cg, ln, st = out
+        p = SWParameters(*parameters)
+        flags = ((_lib.FLAG_BINARY_CIGAR if binary_cigar else 0) | (_lib.FLAG_SCORE_ONLY if score_only else 0) |
+                 (_lib.FLAG_EXTEND_TO_QUERY_END if to_query_end else 0))
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        rc = _lib.lib().mgl_sw_extend_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len),
+            int(max_tl), int(max_ql), p.match, p.mismatch, p.gap_open, p.gap_extend, int(band), int(zdrop), ptr(ext), ptr(cg), int(cigar_stride),
+            ptr(ln), ptr(st), flags)
+        _check(rc, ctx)
+        return out
+
     def align_packed_2bit(self, target_bases, target_base_count, t_start, t_len, query_bases, query_base_count, q_start, q_len,
                           max_tl, max_ql, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,
                           out=None):
@@ -313,7 +371,7 @@ class MicrosoftSmithWaterman:
     @staticmethod
     def fill_kernel_name(timing):
         """Name of the fill kernel a Timing record belongs to (MGL_SW_KERNEL_*)."""
-        return _lib.FILL_KERNEL_NAMES[timing.fill_kernel]
+        return _lib.fill_kernel_name(timing.fill_kernel)
 
     @property
     def ctx(self):
