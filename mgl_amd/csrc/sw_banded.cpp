@@ -1,6 +1,6 @@
 // sw_banded.cpp -- mgl_sw_align_batch_device_banded (include/mgl_sw.h): the GATK function over a diagonal band.  Host side only: argument
 // checks, the workspace slots and the launch of sw_banded_kernel (sw_banded.hip).  Its own translation unit: the context is reached
-// through the accessors at the end of sw_capi.cpp, so the host-sanitizer build of sw_capi.cpp (tests/cpp) needs nothing of the kernel.
+// through the accessors at the end of sw_capi.cpp (sw_ctx_access.h), so the host-sanitizer build of sw_capi.cpp (tests/cpp) needs nothing of the kernel.
 #include "../../include/mgl_sw.h"
 
 #include <hip/hip_runtime.h>
@@ -10,21 +10,9 @@
 #include <mutex>
 #include <string>
 
-#include "sw_banded.h"
+#include "sw_band_host.h"
 
 using namespace mgl_sw_dev;
-
-#define MGL_SW_INTERNAL __attribute__((visibility("hidden")))
-
-namespace mgl_sw_host { // sw_capi.cpp
-MGL_SW_INTERNAL std::mutex &ctx_mutex(mgl_sw_ctx *ctx);
-MGL_SW_INTERNAL int ctx_cus(mgl_sw_ctx *ctx);
-MGL_SW_INTERNAL int64_t ctx_workspace_limit(mgl_sw_ctx *ctx);
-MGL_SW_INTERNAL int ctx_fail(mgl_sw_ctx *ctx, int status, const char *what);
-MGL_SW_INTERNAL int ctx_hip_fail(mgl_sw_ctx *ctx, hipError_t e, const char *where);
-MGL_SW_INTERNAL int ctx_borrow_workspace(mgl_sw_ctx *ctx, hipStream_t st, size_t bytes, void **ws);
-MGL_SW_INTERNAL int ctx_return_workspace(mgl_sw_ctx *ctx, hipStream_t st, int fill_kernel, int launches);
-} // namespace mgl_sw_host
 
 using namespace mgl_sw_host;
 
@@ -69,8 +57,7 @@ int mgl_sw_align_batch_device_banded(mgl_sw_ctx *ctx, void *stream, int64_t n, c
     a.gopen = gopen;
     a.gext = gext;
     a.strategy = strategy;
-    // a band of max(tl, ql) covers a pair's matrix, and no pair beyond BANDED_MAX_LEN passes the range guard
-    a.band = std::min({band, std::max(max_tl, max_ql), BANDED_MAX_LEN});
+    a.band = clamp_band(band, max_tl, max_ql);
     a.max_tl = max_tl;
     a.max_ql = max_ql;
     a.offset = d_offset_out;
@@ -81,21 +68,9 @@ int mgl_sw_align_batch_device_banded(mgl_sw_ctx *ctx, void *stream, int64_t n, c
     a.cigar_len = d_cigar_len_out;
     a.binary_cigar = binary ? 1 : 0;
     a.score_only = score_only ? 1 : 0;
-    // ---- one workspace slot per wave of the grid, sized for the largest pair the bounds admit; where the workspace cannot hold that,
-    // one slot of all there is (a pair that does not fit its slot: MGL_SW_ERR_UNSUPPORTED).  A wave takes every slots-th pair: a
-    // batch larger than the grid is worked off inside the one launch
-    const int64_t limit = std::max<int64_t>(ctx_workspace_limit(ctx), 256) / 256 * 256;
-    const int64_t slot = std::min<int64_t>(banded_slot_bound(std::min(max_tl, BANDED_MAX_LEN), std::min(max_ql, BANDED_MAX_LEN), a.band, score_only), limit);
-    const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({n, (int64_t)ctx_cus(ctx) * BANDED_WAVES_PER_CU, limit / slot}));
-    void *ws = nullptr;
-    const int rc = ctx_borrow_workspace(ctx, st, (size_t)(waves * slot), &ws);
-    if (rc != MGL_SW_OK) return rc;
-    a.ws = static_cast<unsigned char *>(ws);
-    a.slot_bytes = slot;
-    a.slots = (int)waves;
-    const hipError_t e = launch_banded(a, st);
-    if (e != hipSuccess) return ctx_hip_fail(ctx, e, "launch_banded");
-    return ctx_return_workspace(ctx, st, MGL_SW_KERNEL_BANDED, 1);
+    // ---- the slots are sized for the largest pair the bounds admit
+    return launch_on_slots(ctx, st, a, banded_slot_bound(std::min(max_tl, BANDED_MAX_LEN), std::min(max_ql, BANDED_MAX_LEN), a.band, score_only), launch_banded,
+                           "launch_banded", MGL_SW_KERNEL_BANDED);
 }
 
 } // extern "C"

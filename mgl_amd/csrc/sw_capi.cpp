@@ -19,14 +19,12 @@
 #include <string>
 #include <vector>
 
+#include "sw_ctx_access.h"
 #include "sw_device.h"
 
 using namespace mgl_sw_dev;
 
 static_assert(sizeof(mgl_sw_score) == sizeof(Score), "mgl_sw_score layout");
-
-// library-internal entry points shared with sw_batcher.cpp: C linkage, but not exported from the .so
-#define MGL_SW_INTERNAL __attribute__((visibility("hidden")))
 
 namespace {
 
@@ -1478,8 +1476,8 @@ int run_shared_target(mgl_sw_ctx *ctx, hipStream_t stream, int64_t n, const SeqS
 
 } // namespace
 
-// ---- what mgl_sw_local_batch_device_matrix (sw_local.cpp, its own translation unit) needs of a context: C++ names, hidden, declared
-// again at the top of sw_local.cpp.  The caller holds ctx_mutex(ctx) around every other one.
+// ---- what mgl_sw_local_batch_device_matrix (sw_local.cpp, its own translation unit) needs of a context, and the banded and extend entries
+// likewise: C++ names, hidden, declared in sw_ctx_access.h.  The caller holds ctx_mutex(ctx) around every other one.
 namespace mgl_sw_host {
 
 MGL_SW_INTERNAL std::mutex &ctx_mutex(mgl_sw_ctx *ctx) { return ctx->mu; }

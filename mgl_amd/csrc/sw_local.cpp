@@ -1,7 +1,7 @@
 // sw_local.cpp -- mgl_sw_local_batch_device_matrix (include/mgl_sw.h): local Smith-Waterman with a substitution matrix.  Host side only:
 // argument checks, the planner rule, the workspace and the launches of the two kernels (sw_local_lane.hip: kernel A, the packed score
 // pass over tiles that share their target; sw_local.hip: kernel B, any pair in int32 with ends, begin and CIGAR).  Its own translation
-// unit: the context is reached through the accessors at the end of sw_capi.cpp, so the host-sanitizer build of sw_capi.cpp (tests/cpp)
+// unit: the context is reached through the accessors at the end of sw_capi.cpp (sw_ctx_access.h), so the host-sanitizer build of sw_capi.cpp (tests/cpp)
 // needs nothing of the new kernels.
 #include "../../include/mgl_sw.h"
 
@@ -15,27 +15,12 @@
 #include <string>
 #include <vector>
 
+#include "sw_ctx_access.h"
 #include "sw_local.h"
 
 using namespace mgl_sw_dev;
 
 static_assert(sizeof(mgl_sw_local_hit) == 20 && sizeof(LocalHit) == sizeof(mgl_sw_local_hit), "mgl_sw_local_hit layout");
-
-#define MGL_SW_INTERNAL __attribute__((visibility("hidden")))
-
-namespace mgl_sw_host { // sw_capi.cpp
-MGL_SW_INTERNAL std::mutex &ctx_mutex(mgl_sw_ctx *ctx);
-MGL_SW_INTERNAL int ctx_device(mgl_sw_ctx *ctx);
-MGL_SW_INTERNAL int ctx_cus(mgl_sw_ctx *ctx);
-MGL_SW_INTERNAL int64_t ctx_workspace_limit(mgl_sw_ctx *ctx);
-MGL_SW_INTERNAL int ctx_fail(mgl_sw_ctx *ctx, int status, const char *what);
-MGL_SW_INTERNAL int ctx_hip_fail(mgl_sw_ctx *ctx, hipError_t e, const char *where);
-MGL_SW_INTERNAL int ctx_stage_matrix(mgl_sw_ctx *ctx, hipStream_t st, const int8_t *matrix, const uint8_t *code, int8_t **d_matrix, uint8_t **d_code);
-MGL_SW_INTERNAL int ctx_borrow_workspace(mgl_sw_ctx *ctx, hipStream_t st, size_t bytes, void **ws);
-MGL_SW_INTERNAL int ctx_return_workspace(mgl_sw_ctx *ctx, hipStream_t st, int fill_kernel, int launches);
-MGL_SW_INTERNAL int ctx_tile_counter(mgl_sw_ctx *ctx, hipStream_t st, unsigned **ctr, int32_t **fault);
-MGL_SW_INTERNAL int ctx_tile_buffers(mgl_sw_ctx *ctx, hipStream_t st, size_t bytes, void **dev, void **host);
-} // namespace mgl_sw_host
 
 using namespace mgl_sw_host;
 

@@ -83,6 +83,40 @@ def concat(seqs):
     return data, off
 
 
+def _default_stride(max_tl, max_ql, binary_cigar):
+    return max(16, 2 * max(max_tl, max_ql)) * (4 if binary_cigar else 1)
+
+
+def _pack_pairs(refs, alts, dev, cigar_stride, binary_cigar):
+    """Lists of byte strings -> (n, the six device tensors and two bounds the *_device forms take, cigar_stride)."""
+    import torch
+
+    ts, qs = [bytes(x) for x in refs], [bytes(x) for x in alts]
+    assert len(qs) == len(ts)
+    td, toff = concat(ts)
+    qd, qoff = concat(qs)
+    g = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    tlen, qlen = np.diff(toff).astype(np.int32), np.diff(qoff).astype(np.int32)
+    max_tl, max_ql = int(tlen.max(initial=1)), int(qlen.max(initial=1))
+    if cigar_stride is None:
+        cigar_stride = _default_stride(max_tl, max_ql, binary_cigar)
+    pad = np.zeros(8, np.uint8)
+    return len(ts), (g(np.concatenate([td, pad])), g(toff[:-1]), g(tlen), g(np.concatenate([qd, pad])), g(qoff[:-1]), g(qlen), max_tl, max_ql), cigar_stride
+
+
+def _fetch(out, dev, return_status):
+    """The device form's output tensors as numpy arrays, once the stream is done; a pair's status raises unless it is asked for."""
+    import torch
+
+    torch.cuda.synchronize(dev)
+    out = [None if x is None else x.cpu().numpy() for x in out]
+    st = out[-1]
+    if not return_status and st.any():
+        k = int(np.flatnonzero(st)[0])
+        raise _lib.MglSwError(int(st[k]), f"pair {k}")
+    return out
+
+
 class MicrosoftSmithWaterman:
     """Drop-in for the reference's SWAlignerNativeBinding implementation.
 
@@ -157,25 +191,10 @@ class MicrosoftSmithWaterman:
         what align_batch returns (with ``return_status`` the per-pair status array as well, and no exception for a pair's status)."""
         import torch
 
-        ts, qs = [bytes(x) for x in refs], [bytes(x) for x in alts]
-        n = len(ts)
-        assert len(qs) == n
         dev = torch.device("cuda", self._device)
-        td, toff = concat(ts)
-        qd, qoff = concat(qs)
-        g = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
-        tlen, qlen = np.diff(toff).astype(np.int32), np.diff(qoff).astype(np.int32)
-        max_tl, max_ql = int(tlen.max(initial=1)), int(qlen.max(initial=1))
-        if cigar_stride is None:
-            cigar_stride = max(16, 2 * max(max_tl, max_ql)) * (4 if binary_cigar else 1)
-        out = self.align_banded_device(g(np.concatenate([td, np.zeros(8, np.uint8)])), g(toff[:-1]), g(tlen),
-                                       g(np.concatenate([qd, np.zeros(8, np.uint8)])), g(qoff[:-1]), g(qlen), max_tl, max_ql, band, parameters,
-                                       overhang_strategy, cigar_stride, binary_cigar, score_only)
-        torch.cuda.synchronize(dev)
-        off, sc, cg, ln, st = (None if x is None else x.cpu().numpy() for x in out)
-        if not return_status and st.any():
-            k = int(np.flatnonzero(st)[0])
-            raise _lib.MglSwError(int(st[k]), f"pair {k}")
+        n, packed, cigar_stride = _pack_pairs(refs, alts, dev, cigar_stride, binary_cigar)
+        out = self.align_banded_device(*packed, band, parameters, overhang_strategy, cigar_stride, binary_cigar, score_only)
+        off, sc, cg, ln, st = _fetch(out, dev, return_status)
         if score_only:
             res = BatchResult(off, sc, None, None)
         else:
@@ -193,7 +212,7 @@ class MicrosoftSmithWaterman:
         n = int(t_start.numel())
         dev = targets.device
         if cigar_stride is None:
-            cigar_stride = max(16, 2 * max(max_tl, max_ql)) * (4 if binary_cigar else 1)
+            cigar_stride = _default_stride(max_tl, max_ql, binary_cigar)
         if out is None:
             out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 6), dtype=torch.int32, device=dev),
                    None if score_only else torch.empty(n * cigar_stride, dtype=torch.uint8, device=dev),
@@ -217,24 +236,10 @@ class MicrosoftSmithWaterman:
         ``return_status`` the per-pair status array as well, and no exception for a pair's status)."""
         import torch
 
-        ts, qs = [bytes(x) for x in refs], [bytes(x) for x in alts]
-        n = len(ts)
-        assert len(qs) == n
         dev = torch.device("cuda", self._device)
-        td, toff = concat(ts)
-        qd, qoff = concat(qs)
-        g = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
-        tlen, qlen = np.diff(toff).astype(np.int32), np.diff(qoff).astype(np.int32)
-        max_tl, max_ql = int(tlen.max(initial=1)), int(qlen.max(initial=1))
-        if cigar_stride is None:
-            cigar_stride = max(16, 2 * max(max_tl, max_ql)) * (4 if binary_cigar else 1)
-        out = self.extend_device(g(np.concatenate([td, np.zeros(8, np.uint8)])), g(toff[:-1]), g(tlen), g(np.concatenate([qd, np.zeros(8, np.uint8)])),
-                                 g(qoff[:-1]), g(qlen), max_tl, max_ql, band, zdrop, parameters, to_query_end, cigar_stride, binary_cigar, score_only)
-        torch.cuda.synchronize(dev)
-        ext, cg, ln, st = (None if x is None else x.cpu().numpy() for x in out)
-        if not return_status and st.any():
-            k = int(np.flatnonzero(st)[0])
-            raise _lib.MglSwError(int(st[k]), f"pair {k}")
+        n, packed, cigar_stride = _pack_pairs(refs, alts, dev, cigar_stride, binary_cigar)
+        out = self.extend_device(*packed, band, zdrop, parameters, to_query_end, cigar_stride, binary_cigar, score_only)
+        ext, cg, ln, st = _fetch(out, dev, return_status)
         fields = [ext[:, c] for c in range(8)]
         res = ExtendResult(*fields, None, None) if score_only else ExtendResult(*fields, CigarColumn(cg.reshape(n, cigar_stride), ln), ln)
         return (res, st) if return_status else res
@@ -250,7 +255,7 @@ class MicrosoftSmithWaterman:
         n = int(t_start.numel())
         dev = targets.device
         if cigar_stride is None:
-            cigar_stride = max(16, 2 * max(max_tl, max_ql)) * (4 if binary_cigar else 1)
+            cigar_stride = _default_stride(max_tl, max_ql, binary_cigar)
         if out is None:
             out = (torch.empty((n, 8), dtype=torch.int32, device=dev), None if score_only else torch.empty(n * cigar_stride, dtype=torch.uint8, device=dev),
                    None if score_only else torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))

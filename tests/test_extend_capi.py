@@ -81,7 +81,7 @@ def test_without_a_gpu_a_well_formed_call_is_a_device_error():
 
 
 def test_kernel_sources_hold_no_scalar_memory_store():
-    for f in ("sw_extend.hip", "sw_extend.h", "sw_extend.cpp"):
+    for f in ("sw_extend.hip", "sw_extend.h", "sw_extend.cpp", "sw_band_wave.h", "sw_band_host.h", "sw_ctx_access.h"):
         src = open(os.path.join(ROOT, "mgl_amd", "csrc", f)).read().lower()
         for word in ("s_" + "store", "s_" + "buffer_", "s_" + "scratch_", "s_" + "atomic", "s_" + "dcache"):
             assert word not in src, (f, word)

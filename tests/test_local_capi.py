@@ -77,7 +77,7 @@ def test_kernel_ids_mirrored():
 
 
 def test_new_kernel_sources_hold_no_scalar_memory_store():
-    for f in ("sw_local.hip", "sw_local_lane.hip", "sw_local.h", "sw_local.cpp"):
+    for f in ("sw_local.hip", "sw_local_lane.hip", "sw_local.h", "sw_local.cpp", "sw_ctx_access.h"):
         src = open(os.path.join(ROOT, "mgl_amd", "csrc", f)).read().lower()
         for word in ("s_" + "store", "s_" + "buffer_", "s_" + "scratch_", "s_" + "atomic", "s_" + "dcache"):
             assert word not in src, (f, word)
