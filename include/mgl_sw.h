@@ -91,6 +91,7 @@ typedef struct mgl_sw_timing {
 #define MGL_SW_KERNEL_LOCAL 11 /* sw_local_pair_kernel: local alignment, one wave per pair, int32, ends + begin + CIGAR */
 #define MGL_SW_KERNEL_BANDED 12 /* sw_banded_kernel: the GATK function over a diagonal band, one wave per pair, int32 */
 #define MGL_SW_KERNEL_EXTEND (MGL_SW_KERNEL_BANDED + 1) /* 13, sw_extend_kernel: anchored extension with Z-drop over a centred band, one wave per pair, int32 */
+#define MGL_SW_KERNEL_EXTEND_ADAPTIVE (MGL_SW_KERNEL_BANDED + 2) /* 14, sw_extend_adaptive_kernel: the same with the band re-centred every 64 rows (MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND) */
 
 /* What the library WOULD do with a batch: the planner's decisions, without running anything (mgl_sw_explain). */
 typedef struct mgl_sw_plan {
@@ -348,6 +349,11 @@ int mgl_sw_shard_by_cells(int64_t n, const int64_t *t_off, const int64_t *q_off,
 /* MGL_SW_FLAG_EXTEND_TO_QUERY_END (mgl_sw_extend_batch_device only; ignored elsewhere): the CIGAR describes the path to
  * (t_end_qend, ql), the best cell of the query's last column, wherever there is one; see there. */
 #define MGL_SW_FLAG_EXTEND_TO_QUERY_END 0x20
+/* MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND (mgl_sw_extend_batch_device only; ignored elsewhere): the band follows the alignment -- it is
+ * re-centred every MGL_SW_EXTEND_RECENTRE_ROWS target rows on the diagonal of the row maximum; see there.  The number of rows is part
+ * of the function's definition (the outputs depend on it), not an implementation detail. */
+#define MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND 0x40
+#define MGL_SW_EXTEND_RECENTRE_ROWS 64
 int mgl_sw_align_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets,
                               const int64_t *d_t_off, const uint8_t *d_queries,
                               const int64_t *d_q_off, int max_tl, int max_ql, int match,
@@ -547,6 +553,20 @@ int mgl_sw_align_batch_device_banded(mgl_sw_ctx *ctx, void *stream, int64_t n, c
  * (each part rounded as in sw_extend.h); the band does not widen with |ql - tl|, so the formula is monotone and every slot is sized at
  * (max_tl, max_ql): 6 MiB for 10 000 x 10 000 at band 512.  Grid, persistence and workspace limit as for the banded entry.
  * Everything is enqueued on `stream`; the call does not synchronise.  mgl_sw_ctx_get_timing's fill_kernel: MGL_SW_KERNEL_EXTEND.
+ *
+ * MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND: THE BAND FOLLOWS THE ALIGNMENT.  Defined by tests/extend_adaptive_textbook.py; everything above holds
+ * except the band.  Rows are grouped in blocks of R = MGL_SW_EXTEND_RECENTRE_ROWS = 64: row i >= 1 is in block b = (i - 1) / R, row 0
+ * counts with block 0.  Block b has a centre d_b, d_0 = 0, and a cell (i, j), border included, is in the band iff
+ * d_b - band <= j - i <= d_b + band for the block b of its own row.  For b >= 1, d_b = rj(R b) - R b, the diagonal of the smallest
+ * column holding the largest in-band H of row R b (the border column included where it is in that row's band); d_b = d_(b-1) where row
+ * R b has no in-band cell.  A cell has one band, its row's, and an out-of-band cell is minus infinity for every reader: row R b + 1
+ * reads H and E of row R b only where row R b had them under d_(b-1).  |d_b - d_(b-1)| <= band follows.  The border column is in the
+ * band of row i whenever i + d_b - band <= 0; a row has a cell iff i + d_b - band <= ql, and a row without one drops when the rule is
+ * on and is empty when it is off, as above.  rowmax, rj, best, the drop rule, every field of the record and the CIGAR are as above,
+ * over this band.  So `band` need only cover the largest indel between two re-centrings, not the drift summed over the extension.
+ * A pair with tl <= 64 and any pair at band >= tl + ql give exactly the result without the flag.  The band is used as given up to
+ * max_tl + max_ql.  Combines with the three flags above.  A slot holds 4 ceil(tl / 64) bytes more (rounded to 256; not with
+ * MGL_SW_FLAG_SCORE_ONLY), still sized at (max_tl, max_ql).  fill_kernel: MGL_SW_KERNEL_EXTEND_ADAPTIVE.
  */
 typedef struct mgl_sw_extension {
     int32_t score, t_end, q_end, score_qend, t_end_qend, rows_done, dropped, cigar_from;

@@ -19,6 +19,7 @@ FLAG_GROUPED_GEOMETRY = 4
 FLAG_SCORE_ONLY = 8
 FLAG_SHARED_TARGET = 0x10
 FLAG_EXTEND_TO_QUERY_END = 0x20
+FLAG_EXTEND_ADAPTIVE_BAND = 0x40
 OK, ERR_BAD_ARG, ERR_CIGAR_OVERFLOW, ERR_NOMEM, ERR_DEVICE, ERR_UNSUPPORTED = range(6)
 
 # every symbol include/mgl_sw.h declares (tests check that the library exports them all)
@@ -82,13 +83,17 @@ FILL_KERNEL_NAMES = ("sw_dp_kernel", "sw_dp16_kernel", "sw_dp64_kernel", "sw_dp_
                      "sw_local_lane_kernel", "sw_local_pair_kernel", "sw_banded_kernel")
 # MGL_SW_KERNEL_EXTEND: the header spells it MGL_SW_KERNEL_BANDED + 1 and this mirror keeps it beside the tuple, because
 # tests/test_banded_capi.py pins the tuple above at thirteen names and tests/test_capi_host.py ties its length to the header's numeric
-# MGL_SW_KERNEL_* lines; fill_kernel_name() knows both
+# MGL_SW_KERNEL_* lines; fill_kernel_name() knows them.  MGL_SW_KERNEL_EXTEND_ADAPTIVE (MGL_SW_KERNEL_BANDED + 2) likewise
 KERNEL_EXTEND = len(FILL_KERNEL_NAMES)
 EXTEND_KERNEL_NAME = "sw_extend_kernel"
+KERNEL_EXTEND_ADAPTIVE = KERNEL_EXTEND + 1
+EXTEND_ADAPTIVE_KERNEL_NAME = "sw_extend_adaptive_kernel"
 
 
 def fill_kernel_name(kernel_id):
     """MGL_SW_KERNEL_* -> the kernel's name."""
+    if kernel_id == KERNEL_EXTEND_ADAPTIVE:
+        return EXTEND_ADAPTIVE_KERNEL_NAME
     return EXTEND_KERNEL_NAME if kernel_id == KERNEL_EXTEND else FILL_KERNEL_NAMES[kernel_id]
 
 

@@ -1,5 +1,6 @@
-// sw_band_wave.h -- what sw_banded_kernel (sw_banded.hip) and sw_extend_kernel (sw_extend.hip) share: one wave per pair over the cells
-// of a diagonal band, int32 (DESIGN.md sections 9b and 9c).  Device code, included by those two files only; every function is inlined
+// sw_band_wave.h -- what sw_banded_kernel (sw_banded.hip), sw_extend_kernel (sw_extend.hip) and sw_extend_adaptive_kernel
+// (sw_extend_adaptive.hip) share: one wave per pair over the cells of a diagonal band, int32 (DESIGN.md sections 9b to 9d).  Device code,
+// included by those three files only; every function is inlined
 // into its kernel (docs/history.md C.000000 compares the code objects with those of the kernels that held a copy each).
 //
 // The 64 lanes hold 64 consecutive target rows (a strip) on an anti-diagonal: at step s lane l of strip k is at column c0 + s - l,

@@ -1,5 +1,6 @@
 // sw_extend.cpp -- mgl_sw_extend_batch_device (include/mgl_sw.h): anchored extension with Z-drop over a band centred on the main
-// diagonal.  Host side only: argument checks, the workspace slots and the launch of sw_extend_kernel (sw_extend.hip).  Its own
+// diagonal, or -- MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND -- re-centred every 64 rows.  Host side only: argument checks, the workspace slots and
+// the launch of sw_extend_kernel (sw_extend.hip) or sw_extend_adaptive_kernel (sw_extend_adaptive.hip).  Its own
 // translation unit, like sw_banded.cpp: the context is reached through the accessors at the end of sw_capi.cpp (sw_ctx_access.h), so the host-sanitizer
 // build of sw_capi.cpp (tests/cpp) needs nothing of the kernel.
 #include "../../include/mgl_sw.h"
@@ -17,6 +18,7 @@
 using namespace mgl_sw_dev;
 
 static_assert(sizeof(mgl_sw_extension) == sizeof(Extension), "mgl_sw_extension and the kernel's record are one layout");
+static_assert(MGL_SW_EXTEND_RECENTRE_ROWS == EXTEND_RECENTRE_ROWS, "the band is re-centred once per strip of the kernel");
 
 using namespace mgl_sw_host;
 
@@ -28,6 +30,7 @@ int mgl_sw_extend_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const u
                                char *d_cigar_out, int cigar_stride, int32_t *d_cigar_len_out, int32_t *d_status_out, int flags)
 {
     const bool score_only = (flags & MGL_SW_FLAG_SCORE_ONLY) != 0, binary = (flags & MGL_SW_FLAG_BINARY_CIGAR) != 0;
+    const bool adaptive = (flags & MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND) != 0;
     // ---- arguments first: nothing below touches a device before they are known good
     const char *bad = nullptr;
     if (n < 0) bad = "n < 0";
@@ -57,7 +60,9 @@ int mgl_sw_extend_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const u
     a.mismatch = mismatch;
     a.gopen = gopen;
     a.gext = gext;
-    a.band = clamp_band(band, max_tl, max_ql);
+    // a fixed band of max(tl, ql) covers a pair's matrix; one that follows the path does so wherever it stands only from tl + ql on, so
+    // the clamp that keeps the geometry in int32 (|d_k| <= max(tl, ql) <= BANDED_MAX_LEN, see sw_extend_adaptive.hip) is wider there
+    a.band = adaptive ? (int)std::min<int64_t>({(int64_t)band, (int64_t)max_tl + max_ql, 2 * (int64_t)BANDED_MAX_LEN}) : clamp_band(band, max_tl, max_ql);
     a.zdrop = zdrop;
     a.max_tl = max_tl;
     a.max_ql = max_ql;
@@ -71,8 +76,11 @@ int mgl_sw_extend_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const u
     a.to_query_end = (flags & MGL_SW_FLAG_EXTEND_TO_QUERY_END) ? 1 : 0;
     // ---- the band does not widen with |ql - tl|, so a slot's formula is monotone in both lengths and the largest pair the bounds admit
     // is the bounds themselves
-    return launch_on_slots(ctx, st, a, extend_pair_bytes(std::min(max_tl, BANDED_MAX_LEN), std::min(max_ql, BANDED_MAX_LEN), a.band, score_only), launch_extend,
-                           "launch_extend", MGL_SW_KERNEL_EXTEND);
+    const int cap_tl = std::min(max_tl, BANDED_MAX_LEN), cap_ql = std::min(max_ql, BANDED_MAX_LEN);
+    if (adaptive)
+        return launch_on_slots(ctx, st, a, extend_adaptive_pair_bytes(cap_tl, cap_ql, a.band, score_only), launch_extend_adaptive, "launch_extend_adaptive",
+                               MGL_SW_KERNEL_EXTEND_ADAPTIVE);
+    return launch_on_slots(ctx, st, a, extend_pair_bytes(cap_tl, cap_ql, a.band, score_only), launch_extend, "launch_extend", MGL_SW_KERNEL_EXTEND);
 }
 
 } // extern "C"

@@ -30,11 +30,21 @@ __host__ __device__ inline int64_t extend_pair_bytes(int tl, int ql, int band, b
     return banded_carry_bytes(ql) + (score_only ? 0 : banded_elem_bytes(tl, ql) + (int64_t)((tl + 63) / 64) * extend_strip_steps(ql, band) * 32);
 }
 
+// ---- MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND (the definition is tests/extend_adaptive_textbook.py's, which mirrors the
+// formula): the band is re-centred every EXTEND_RECENTRE_ROWS rows, a strip's sweep is as wide as before, and behind the decisions the
+// slot keeps one int32 per strip, the strip's centre d_k, which the walk reads back.  Still monotone in tl and in ql
+constexpr int EXTEND_RECENTRE_ROWS = 64; // == MGL_SW_EXTEND_RECENTRE_ROWS: the kernel's strip, and part of the function's definition
+__host__ __device__ inline int64_t extend_centre_bytes(int tl) { return ((int64_t)((tl + 63) / 64) * 4 + 255) / 256 * 256; }
+__host__ __device__ inline int64_t extend_adaptive_pair_bytes(int tl, int ql, int band, bool score_only)
+{
+    return extend_pair_bytes(tl, ql, band, score_only) + (score_only ? 0 : extend_centre_bytes(tl));
+}
+
 struct ExtendArgs {
     SeqSet t, q;              // ASCII, per-pair start + length (len arrays set)
     int64_t n;                // pairs 0 .. n - 1: wave w takes pairs w, w + slots, w + 2 slots, ...
     int match, mismatch, gopen, gext; // normalised
-    int band;                 // at most max(max_tl, max_ql)
+    int band;                 // at most max(max_tl, max_ql); launch_extend_adaptive: at most 2 BANDED_MAX_LEN
     int zdrop;                // < 0: off
     int max_tl, max_ql;       // the caller's bounds (a pair beyond them: MGL_SW_ERR_BAD_ARG)
     Extension *ext;
@@ -51,6 +61,7 @@ struct ExtendArgs {
 };
 
 hipError_t launch_extend(const ExtendArgs &a, hipStream_t stream);
+hipError_t launch_extend_adaptive(const ExtendArgs &a, hipStream_t stream); // sw_extend_adaptive.hip
 
 } // namespace mgl_sw_dev
 

@@ -229,23 +229,26 @@ class MicrosoftSmithWaterman:
         return out
 
     def extend(self, refs, alts, band, zdrop, parameters=GATK_PARAMETERS, to_query_end=False, cigar_stride=None, binary_cigar=False,
-               score_only=False, return_status=False):
+               score_only=False, return_status=False, adaptive_band=False):
         """mgl_sw_extend_batch_device over lists of byte strings: the extension of alts[k] along refs[k] from the anchored start (0, 0)
         to a free end, over the cells with -band <= j - i <= band, stopped by the Z-drop rule (``zdrop`` < 0: off).  NOT a reference
-        function.  Returns ExtendResult: the eight fields of mgl_sw_extension as arrays, the CIGARs and their lengths (with
-        ``return_status`` the per-pair status array as well, and no exception for a pair's status)."""
+        function.  ``adaptive_band``: the band is re-centred every 64 target rows on the diagonal of the row maximum
+        (MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND), so ``band`` need only cover the largest indel between two re-centrings.  Returns
+        ExtendResult: the eight fields of mgl_sw_extension as arrays, the CIGARs and their lengths (with ``return_status`` the per-pair
+        status array as well, and no exception for a pair's status)."""
         import torch
 
         dev = torch.device("cuda", self._device)
         n, packed, cigar_stride = _pack_pairs(refs, alts, dev, cigar_stride, binary_cigar)
-        out = self.extend_device(*packed, band, zdrop, parameters, to_query_end, cigar_stride, binary_cigar, score_only)
+        out = self.extend_device(*packed, band, zdrop, parameters, to_query_end, cigar_stride, binary_cigar, score_only,
+                                 adaptive_band=adaptive_band)
         ext, cg, ln, st = _fetch(out, dev, return_status)
         fields = [ext[:, c] for c in range(8)]
         res = ExtendResult(*fields, None, None) if score_only else ExtendResult(*fields, CigarColumn(cg.reshape(n, cigar_stride), ln), ln)
         return (res, st) if return_status else res
 
     def extend_device(self, targets, t_start, t_len, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters=GATK_PARAMETERS,
-                      to_query_end=False, cigar_stride=None, binary_cigar=False, score_only=False, out=None):
+                      to_query_end=False, cigar_stride=None, binary_cigar=False, score_only=False, out=None, adaptive_band=False):
         """The device-tensor form: torch tensors on this context's GPU (uint8 bytes, int64 starts, int32 lengths); enqueued on the current
         stream, not synchronised.  Returns (extensions[n, 8], cigar bytes[n * stride] or None, cigar lengths or None, status) tensors;
         ``out``: such a tuple to write into."""
@@ -262,7 +265,7 @@ class MicrosoftSmithWaterman:
         ext, cg, ln, st = out
         p = SWParameters(*parameters)
         flags = ((_lib.FLAG_BINARY_CIGAR if binary_cigar else 0) | (_lib.FLAG_SCORE_ONLY if score_only else 0) |
-                 (_lib.FLAG_EXTEND_TO_QUERY_END if to_query_end else 0))
+                 (_lib.FLAG_EXTEND_TO_QUERY_END if to_query_end else 0) | (_lib.FLAG_EXTEND_ADAPTIVE_BAND if adaptive_band else 0))
         ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
         rc = _lib.lib().mgl_sw_extend_batch_device(
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len),
