@@ -577,6 +577,60 @@ int mgl_sw_extend_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const u
                                char *d_cigar_out, int cigar_stride, int32_t *d_cigar_len_out, int32_t *d_status_out, int flags);
 
 /*
+ * TWO-SIDED SEED EXTENSION (NOT a reference function; opt-in): a seed in the middle of a read extended to the left and to the right
+ * with mgl_sw_extend_batch_device's function and joined into one alignment, all on the device.  Defined by
+ * tests/seed_extend_textbook.py.  Per pair: a target window T of tl >= 1 and a query Q of ql >= 1 bytes as above, and a seed
+ * (d_seed_t, d_seed_q, d_seed_len: int32 per pair) st, sq, sl that lays T[st .. st + sl) against Q[sq .. sq + sl): sl >= 1, 0 <= st,
+ * st + sl <= tl, 0 <= sq, sq + sl <= ql.  Per call: the parameters, band, zdrop and the flags of mgl_sw_extend_batch_device, which hold
+ * for each side unchanged (the band clamp is that entry's, for the flag in force).
+ *   Seed: one `sl M` element; seed_score = the sum of match / mismatch over its sl columns (a seed need not be exact).
+ *   Right side: the extension of Q[sq + sl ..) along T[st + sl ..) as defined above (with MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND: as defined
+ *   there).  Left side: the same function on the REVERSED flanks, reverse(T[0 .. st)) and reverse(Q[0 .. sq)); its CIGAR elements are
+ *   taken in reverse order.  What is said there about long deletions and the band holds for each side on its own.
+ *   A side with an empty flank never reaches the extension: with an empty query flank (the target flank empty or not) its record is
+ *   all zero -- the empty extension, which ends on column ql = 0 --; with the target flank alone empty it is all zero except
+ *   score_qend = -0x40000000, t_end_qend = -1 (no row reaches column ql).  Both have an empty CIGAR.
+ *   A side contributes the H of the cell its CIGAR starts from: score_qend at (t_end_qend, flank ql) where its cigar_from is 1,
+ *   otherwise score at (t_end, q_end).
+ * mgl_sw_seed_alignment: score = left contribution + seed_score + right contribution; t_beg, t_end, q_beg, q_end, half open, in the
+ * window's and the query's coordinates: t_beg = st - the left start cell's row, t_end = st + sl + the right start cell's row, the query
+ * likewise with the columns; seed_score; dropped and cigar_from: the sides' values, bit 0 left, bit 1 right.
+ * d_left_out, d_right_out (optional, each may be NULL): the two sides' mgl_sw_extension in FLANK coordinates (the left one on the
+ * reversed flanks), as mgl_sw_extend_batch_device gives them, or the records above for an empty flank.
+ * The CIGAR: the left side's elements last to first, `sl M`, the right side's first to last, adjacent equal operations merged (only
+ * the seed's neighbours can be); M / I / D, no clips -- q_beg / q_end say what a soft clip would.  It spends exactly t_end - t_beg
+ * target and q_end - q_beg query bases.
+ * flags: MGL_SW_FLAG_EXTEND_TO_QUERY_END, MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND, MGL_SW_FLAG_BINARY_CIGAR, MGL_SW_FLAG_SCORE_ONLY (records only;
+ * d_cigar_out / d_cigar_len_out may be NULL); others are ignored.  The call fails before any device work with MGL_SW_ERR_BAD_ARG on
+ * n < 0, a null sequence / start / length / seed array, a null d_aln_out, band < 0, max_tl < 1 or max_ql < 1, and -- without
+ * MGL_SW_FLAG_SCORE_ONLY -- a null CIGAR array or a stride below 2 (4 for binary); with MGL_SW_ERR_DEVICE without a GPU.
+ * d_status_out (optional): MGL_SW_ERR_BAD_ARG for a length below 1 or above max_tl / max_ql or a seed that breaks the inequalities
+ * above; MGL_SW_ERR_UNSUPPORTED where a non-empty side is outside the banded range guard or too large for one workspace slot, or the
+ * pair has a length above 2^28 or max(match, |mismatch|) * sl > 2^29; MGL_SW_ERR_CIGAR_OVERFLOW where the JOINED CIGAR does not fit
+ * cigar_stride, and only then (a side's internal row holds as many elements as a joined CIGAR of cigar_stride bytes can have, or as
+ * max_tl + max_ql admits: sw_seed_extend.h).  A pair with a non-zero status gets an all-zero record, all-zero side records, a
+ * cigar_len of 0 and no byte of its CIGAR row written; nor is any byte of a row at or beyond that pair's cigar_len.
+ * Device work, all on `stream`, no synchronisation: sw_seed_split_kernel (seed checks, flank descriptors, the reversed copies of the
+ * left flanks; the right flanks are read in place), the extension kernel once over the left and once over the right flanks, and
+ * sw_seed_join_kernel (seed score, record, joined CIGAR).  The staging -- per pair about max_tl + max_ql bytes of reversed flanks, 150
+ * bytes of descriptors and records and two internal CIGAR rows of at most 2 cigar_stride bytes -- and the extension slots come out of
+ * one borrowing of the context's workspace and count against its limit: a batch whose staging is more than half the limit is worked
+ * off in chunks of as many pairs as half the limit holds (one pair a chunk where half the limit does not hold one: its staging then
+ * takes more than half), and a limit that does not hold one pair's staging beside a slot fails with MGL_SW_ERR_NOMEM.  Slots, grid and
+ * persistence as for mgl_sw_extend_batch_device.  mgl_sw_ctx_get_timing's fill_kernel: MGL_SW_KERNEL_EXTEND, or
+ * MGL_SW_KERNEL_EXTEND_ADAPTIVE with the flag -- the fill that ran; dp_launches counts two per chunk.
+ */
+typedef struct mgl_sw_seed_alignment {
+    int32_t score, t_beg, t_end, q_beg, q_end, seed_score, dropped, cigar_from;
+} mgl_sw_seed_alignment;
+int mgl_sw_extend_seed_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets, const int64_t *d_t_start,
+                                    const int32_t *d_t_len, const uint8_t *d_queries, const int64_t *d_q_start, const int32_t *d_q_len,
+                                    const int32_t *d_seed_t, const int32_t *d_seed_q, const int32_t *d_seed_len, int max_tl, int max_ql, int match,
+                                    int mismatch, int gopen, int gext, int band, int zdrop, mgl_sw_seed_alignment *d_aln_out,
+                                    mgl_sw_extension *d_left_out, mgl_sw_extension *d_right_out, char *d_cigar_out, int cigar_stride,
+                                    int32_t *d_cigar_len_out, int32_t *d_status_out, int flags);
+
+/*
  * Logical backtrack matrix of one pair, the reference's calculateMatrix
  * (sw_scalar.h:7 / sw.cpp:5-146): btr is (tl+1)*(ql+1) int32 row-major with
  * row 0 / column 0 zero, +k = k rows up (deletion run), -k = k columns left

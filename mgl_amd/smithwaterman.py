@@ -36,6 +36,7 @@ ScoreMax = namedtuple("ScoreMax", "mqe mqe_t max max_t max_q seg_length")
 
 BatchResult = namedtuple("BatchResult", "offsets scores cigars cigar_len")
 ExtendResult = namedtuple("ExtendResult", "score t_end q_end score_qend t_end_qend rows_done dropped cigar_from cigars cigar_len")
+SeedExtendResult = namedtuple("SeedExtendResult", "score t_beg t_end q_beg q_end seed_score dropped cigar_from cigars cigar_len")
 
 
 class CigarColumn:
@@ -271,6 +272,60 @@ class MicrosoftSmithWaterman:
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len),
             int(max_tl), int(max_ql), p.match, p.mismatch, p.gap_open, p.gap_extend, int(band), int(zdrop), ptr(ext), ptr(cg), int(cigar_stride),
             ptr(ln), ptr(st), flags)
+        _check(rc, ctx)
+        return out
+
+    def extend_seed(self, refs, alts, seeds, band, zdrop, parameters=GATK_PARAMETERS, to_query_end=False, cigar_stride=None, binary_cigar=False,
+                    score_only=False, return_status=False, adaptive_band=False, return_sides=False):
+        """mgl_sw_extend_seed_batch_device over lists of byte strings: ``seeds[k]`` = (st, sq, sl) lays refs[k][st:st + sl] against
+        alts[k][sq:sq + sl]; the seed is extended to the right and -- on the reversed flanks -- to the left with the function of
+        ``extend`` (same band, zdrop and options on each side), and the two sides are joined across the seed into one alignment on the
+        device.  NOT a reference function.  Returns SeedExtendResult: the eight fields of mgl_sw_seed_alignment as arrays (spans half
+        open, in the coordinates of refs[k] and alts[k]), the joined CIGARs (M / I / D, no clips) and their lengths; with
+        ``return_sides`` also the two sides' records as int32 arrays [n, 8] (mgl_sw_extension, in flank coordinates), with
+        ``return_status`` the per-pair status array (and no exception for a pair's status): (result[, left, right][, status])."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        n, packed, cigar_stride = _pack_pairs(refs, alts, dev, cigar_stride, binary_cigar)
+        sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.int32).reshape(n, 3).T)
+        seed_t, seed_q, seed_len = (torch.from_numpy(sd[c].copy()).to(dev) for c in range(3))
+        out = self.extend_seed_device(*packed[:6], seed_t, seed_q, seed_len, *packed[6:], band, zdrop, parameters, to_query_end, cigar_stride,
+                                      binary_cigar, score_only, adaptive_band=adaptive_band, sides=return_sides)
+        aln, left, right, cg, ln, st = _fetch(out, dev, return_status)
+        fields = [aln[:, c] for c in range(8)]
+        res = SeedExtendResult(*fields, None, None) if score_only else SeedExtendResult(*fields, CigarColumn(cg.reshape(n, cigar_stride), ln), ln)
+        ret = (res,) + ((left, right) if return_sides else ()) + ((st,) if return_status else ())
+        return ret if len(ret) > 1 else res
+
+    def extend_seed_device(self, targets, t_start, t_len, queries, q_start, q_len, seed_t, seed_q, seed_len, max_tl, max_ql, band, zdrop,
+                           parameters=GATK_PARAMETERS, to_query_end=False, cigar_stride=None, binary_cigar=False, score_only=False, out=None,
+                           adaptive_band=False, sides=False):
+        """The device-tensor form: torch tensors on this context's GPU (uint8 bytes, int64 starts, int32 lengths and seeds); enqueued on
+        the current stream, not synchronised.  Returns (alignments[n, 8], left[n, 8] or None, right[n, 8] or None, cigar bytes
+        [n * stride] or None, cigar lengths or None, status) tensors -- the side records with ``sides`` --; ``out``: such a tuple to
+        write into."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(t_start.numel())
+        dev = targets.device
+        if cigar_stride is None:
+            cigar_stride = _default_stride(max_tl, max_ql, binary_cigar)
+        if out is None:
+            rec = lambda: torch.empty((n, 8), dtype=torch.int32, device=dev)  # noqa: E731
+            out = (rec(), rec() if sides else None, rec() if sides else None,
+                   None if score_only else torch.empty(n * cigar_stride, dtype=torch.uint8, device=dev),
+                   None if score_only else torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+        aln, left, right, cg, ln, st = out
+        p = SWParameters(*parameters)
+        flags = ((_lib.FLAG_BINARY_CIGAR if binary_cigar else 0) | (_lib.FLAG_SCORE_ONLY if score_only else 0) |
+                 (_lib.FLAG_EXTEND_TO_QUERY_END if to_query_end else 0) | (_lib.FLAG_EXTEND_ADAPTIVE_BAND if adaptive_band else 0))
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        rc = _lib.lib().mgl_sw_extend_seed_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len),
+            ptr(seed_t), ptr(seed_q), ptr(seed_len), int(max_tl), int(max_ql), p.match, p.mismatch, p.gap_open, p.gap_extend, int(band), int(zdrop),
+            ptr(aln), ptr(left), ptr(right), ptr(cg), int(cigar_stride), ptr(ln), ptr(st), flags)
         _check(rc, ctx)
         return out
 
