@@ -631,6 +631,75 @@ int mgl_sw_extend_seed_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
                                     int32_t *d_cigar_len_out, int32_t *d_status_out, int flags);
 
 /*
+ * CHAIN ALIGNMENT (NOT a reference function; opt-in): what a long-read mapper hands an aligner is a chain, several colinear anchors
+ * per read.  The left side of the first anchor and the right side of the last one are extended as mgl_sw_extend_seed_batch_device
+ * extends a seed's, every gap between two consecutive anchors is filled GLOBALLY over a diagonal band, and all of it is joined into
+ * one alignment on the device.  Defined by tests/chain_textbook.py.  Per pair p: a target window T of tl >= 1 and a query Q of
+ * ql >= 1 bytes as above, and K >= 1 anchors: d_anchor_start (int64, n + 1 entries, ascending, CSR into the anchor arrays: pair p has
+ * anchors d_anchor_start[p] .. d_anchor_start[p + 1] - 1, all inside [0, total_anchors)), d_anchor_t, d_anchor_q, d_anchor_len
+ * (int32 per anchor): anchor k lays T[st_k .. st_k + sl_k) against Q[sq_k .. sq_k + sl_k), sl_k >= 1, 0 <= st_0, 0 <= sq_0,
+ * st_k + sl_k <= st_(k+1) and sq_k + sl_k <= sq_(k+1), and the last anchor ends inside the window and the query.  Per call: the
+ * parameters, band, zdrop and the flags of mgl_sw_extend_seed_batch_device.
+ *   Anchors: one `sl_k M` element each; anchor_score = the sum of match / mismatch over all anchors' columns (they need not be exact).
+ *   Left and right side: exactly those of mgl_sw_extend_seed_batch_device, the left side of anchor 0 on the reversed flanks and the
+ *   right side of anchor K - 1 -- the records of an empty flank, cigar_from and what a side contributes included.
+ *   Gap k, between anchors k and k + 1: T[st_k + sl_k .. st_(k+1)) against Q[sq_k + sl_k .. sq_(k+1)), gt and gq bases.
+ *   gt = gq = 0: no element, score 0.  gt = 0 < gq: `gq I`, score -(gopen + (gq - 1) gext).  gq = 0 < gt: `gt D`, likewise.
+ *   Otherwise the global fill: mgl_sw_align_batch_device_banded's function under MGL_SW_OS_INDEL on the gap -- its band rule
+ *   (lo = min(0, gq - gt) - band, hi = max(0, gq - gt) + band: both corners are in the band), gap-penalty borders on both axes, its
+ *   recurrence, priorities, run lengths and minus infinity, its walk from (gt, gq) back to (0, 0) -- and the gap's score is
+ *   H(gt, gq), which that entry does not return.  Always the plain band rule, also with MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND, which
+ *   holds for the two sides only.  LIMIT: there is no Z-drop inside a gap; a gap is aligned end to end whatever it costs.
+ * mgl_sw_chain_alignment: score = left contribution + anchor_score + the gaps' scores + right contribution; t_beg, t_end, q_beg,
+ * q_end half open, as in mgl_sw_seed_alignment with st_0 in front and the last anchor's end behind; anchor_score; dropped and
+ * cigar_from: the sides' values, bit 0 left, bit 1 right.  For K = 1 the record is bit for bit mgl_sw_seed_alignment.
+ * d_left_out, d_right_out (optional): the sides' records, as there.  d_gap_score_out (optional): one int32 per anchor index, the
+ * score of the gap behind that anchor; 0 for a pair's last anchor, for the anchors of a pair with a non-zero status and for anchors
+ * that belong to no pair.
+ * The CIGAR: the left side's elements last to first, anchor 0, gap 0, anchor 1, ..., anchor K - 1, the right side's elements,
+ * adjacent equal operations merged (only an M next to an anchor can be; two anchors merge across an empty gap); M / I / D.  It spends
+ * exactly t_end - t_beg target and q_end - q_beg query bases.
+ * max_gap_tl, max_gap_ql (>= 0): the caller's bounds on gt and gq of the gaps that have bases on both sides; they size the fill's
+ * slots and the gaps' internal rows as max_tl and max_ql size a side's.
+ * flags: as mgl_sw_extend_seed_batch_device.  The call fails before any device work with MGL_SW_ERR_BAD_ARG on n < 0 or above 2^30,
+ * total_anchors < 0 or above 2^30, a null sequence / start / length / anchor array, a null d_aln_out, band < 0, max_tl < 1 or
+ * max_ql < 1, max_gap_tl < 0 or max_gap_ql < 0, and -- without MGL_SW_FLAG_SCORE_ONLY -- a null CIGAR array or a stride below 2
+ * (4 for binary); with MGL_SW_ERR_DEVICE without a GPU.
+ * d_status_out (optional), in this order: MGL_SW_ERR_BAD_ARG for a length below 1 or above max_tl / max_ql, for K < 1 or a range of
+ * d_anchor_start that descends or leaves [0, total_anchors), for an anchor that breaks an inequality above, and for a pair whose
+ * range shares an anchor with that of a pair of lower index (which keeps the anchor);
+ * MGL_SW_ERR_UNSUPPORTED where a non-empty side is refused as by mgl_sw_extend_seed_batch_device, where a gap with bases on both
+ * sides is longer than max_gap_tl / max_gap_ql, outside the banded range guard or too large for one workspace slot, where a length
+ * is above 2^28, and where the pair fails the sum guard
+ *   max(match, |mismatch|) min(tl, ql) + 2 gopen (K + 1) + gext (tl + ql) <= 2^30
+ * -- the sum of the banded range guard's bounds over the pair's K + 1 filled segments and K anchors, so that every partial sum of
+ * segment scores stays in an int32; MGL_SW_ERR_CIGAR_OVERFLOW where the JOINED CIGAR does not fit cigar_stride, and only then (the
+ * internal row of a side or a gap holds as many elements as a joined CIGAR of cigar_stride bytes can have: sw_chain.h).  A pair with
+ * a non-zero status gets an all-zero record, all-zero side records, a cigar_len of 0 and no byte of its CIGAR row written; nor is
+ * any byte of a row at or beyond that pair's cigar_len.
+ * Device work, all on `stream`, no synchronisation: sw_chain_split_kernel (the checks, the flank descriptors and the reversed left
+ * flanks, one gap descriptor per anchor), the extension kernel once over the left and once over the right flanks,
+ * sw_gap_fill_kernel (one wave per gap, persistent on slots) and sw_chain_join_kernel (anchor scores, record, d_gap_score_out, joined
+ * CIGAR).  The staging -- per pair what mgl_sw_extend_seed_batch_device stages, per anchor 16 bytes and an internal CIGAR row of at
+ * most 2 cigar_stride and at most 4 (max_gap_tl + max_gap_ql) bytes -- and the slots come out of one borrowing of the context's
+ * workspace and count against its limit.  The extension slots are sized at (max_tl, max_ql), the fill's as
+ * mgl_sw_align_batch_device_banded sizes them at (max_gap_tl, max_gap_ql, band); the two kinds follow one another on the stream and
+ * share one region behind the staging.  The anchor counts are device data, so the batch is staged whole: a limit that does not hold
+ * its staging beside a slot fails with MGL_SW_ERR_NOMEM, and the caller splits the batch.  mgl_sw_ctx_get_timing's fill_kernel:
+ * MGL_SW_KERNEL_EXTEND, or MGL_SW_KERNEL_EXTEND_ADAPTIVE with the flag -- the extension that ran; dp_launches counts three.
+ */
+typedef struct mgl_sw_chain_alignment {
+    int32_t score, t_beg, t_end, q_beg, q_end, anchor_score, dropped, cigar_from;
+} mgl_sw_chain_alignment;
+int mgl_sw_align_chain_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets, const int64_t *d_t_start,
+                                    const int32_t *d_t_len, const uint8_t *d_queries, const int64_t *d_q_start, const int32_t *d_q_len,
+                                    const int64_t *d_anchor_start, const int32_t *d_anchor_t, const int32_t *d_anchor_q, const int32_t *d_anchor_len,
+                                    int64_t total_anchors, int max_tl, int max_ql, int max_gap_tl, int max_gap_ql, int match, int mismatch, int gopen,
+                                    int gext, int band, int zdrop, mgl_sw_chain_alignment *d_aln_out, mgl_sw_extension *d_left_out,
+                                    mgl_sw_extension *d_right_out, int32_t *d_gap_score_out, char *d_cigar_out, int cigar_stride,
+                                    int32_t *d_cigar_len_out, int32_t *d_status_out, int flags);
+
+/*
  * Logical backtrack matrix of one pair, the reference's calculateMatrix
  * (sw_scalar.h:7 / sw.cpp:5-146): btr is (tl+1)*(ql+1) int32 row-major with
  * row 0 / column 0 zero, +k = k rows up (deletion run), -k = k columns left

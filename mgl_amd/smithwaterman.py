@@ -37,6 +37,7 @@ ScoreMax = namedtuple("ScoreMax", "mqe mqe_t max max_t max_q seg_length")
 BatchResult = namedtuple("BatchResult", "offsets scores cigars cigar_len")
 ExtendResult = namedtuple("ExtendResult", "score t_end q_end score_qend t_end_qend rows_done dropped cigar_from cigars cigar_len")
 SeedExtendResult = namedtuple("SeedExtendResult", "score t_beg t_end q_beg q_end seed_score dropped cigar_from cigars cigar_len")
+ChainAlignResult = namedtuple("ChainAlignResult", "score t_beg t_end q_beg q_end anchor_score dropped cigar_from cigars cigar_len")
 
 
 class CigarColumn:
@@ -326,6 +327,74 @@ class MicrosoftSmithWaterman:
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len),
             ptr(seed_t), ptr(seed_q), ptr(seed_len), int(max_tl), int(max_ql), p.match, p.mismatch, p.gap_open, p.gap_extend, int(band), int(zdrop),
             ptr(aln), ptr(left), ptr(right), ptr(cg), int(cigar_stride), ptr(ln), ptr(st), flags)
+        _check(rc, ctx)
+        return out
+
+    def align_chain(self, refs, alts, chains, band, zdrop, parameters=GATK_PARAMETERS, to_query_end=False, cigar_stride=None, binary_cigar=False,
+                    score_only=False, return_status=False, adaptive_band=False, return_sides=False, return_gap_scores=False, max_gap=None):
+        """mgl_sw_align_chain_batch_device over lists of byte strings: ``chains[k]`` = a list of anchors (st, sq, sl), colinear and in
+        order, each laying refs[k][st:st + sl] against alts[k][sq:sq + sl].  The left side of the first anchor and the right side of the
+        last one are extended as ``extend_seed`` extends a seed's, every gap between two anchors is filled globally over the band, and
+        all of it is joined into one alignment on the device.  NOT a reference function.  ``max_gap``: (max_gap_tl, max_gap_ql), by
+        default the largest gap of the batch.  Returns ChainAlignResult: the eight fields of mgl_sw_chain_alignment as arrays, the
+        joined CIGARs and their lengths; with ``return_sides`` also the two sides' records [n, 8], with ``return_gap_scores`` the int32
+        array of one gap score per anchor (in the order of the chains, 0 behind a pair's last anchor), with ``return_status`` the
+        per-pair status array (and no exception for a pair's status): (result[, left, right][, gap scores][, status])."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        n, packed, cigar_stride = _pack_pairs(refs, alts, dev, cigar_stride, binary_cigar)
+        assert len(chains) == n
+        start = np.zeros(n + 1, np.int64)
+        if n:
+            np.cumsum([len(c) for c in chains], out=start[1:])
+        flat = np.asarray([a for c in chains for a in c], dtype=np.int32).reshape(-1, 3)
+        if max_gap is None:
+            gt = gq = 0
+            for c in chains:
+                for (st, sq, sl), (nt, nq, _) in zip(c, c[1:]):
+                    gt, gq = max(gt, nt - st - sl), max(gq, nq - sq - sl)
+            max_gap = (max(gt, 0), max(gq, 0))
+        g = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+        out = self.align_chain_device(*packed[:6], g(start), g(flat[:, 0]), g(flat[:, 1]), g(flat[:, 2]), *packed[6:], max_gap[0], max_gap[1], band, zdrop,
+                                      parameters, to_query_end, cigar_stride, binary_cigar, score_only, adaptive_band=adaptive_band, sides=return_sides,
+                                      gap_scores=return_gap_scores)
+        aln, left, right, gs, cg, ln, st = _fetch(out, dev, return_status)
+        fields = [aln[:, c] for c in range(8)]
+        res = ChainAlignResult(*fields, None, None) if score_only else ChainAlignResult(*fields, CigarColumn(cg.reshape(n, cigar_stride), ln), ln)
+        ret = (res,) + ((left, right) if return_sides else ()) + ((gs,) if return_gap_scores else ()) + ((st,) if return_status else ())
+        return ret if len(ret) > 1 else res
+
+    def align_chain_device(self, targets, t_start, t_len, queries, q_start, q_len, anchor_start, anchor_t, anchor_q, anchor_len, max_tl, max_ql,
+                           max_gap_tl, max_gap_ql, band, zdrop, parameters=GATK_PARAMETERS, to_query_end=False, cigar_stride=None, binary_cigar=False,
+                           score_only=False, out=None, adaptive_band=False, sides=False, gap_scores=False):
+        """The device-tensor form: torch tensors on this context's GPU (uint8 bytes, int64 starts and ``anchor_start`` [n + 1], int32
+        lengths and anchors); enqueued on the current stream, not synchronised.  Returns (alignments[n, 8], left[n, 8] or None,
+        right[n, 8] or None, gap scores [anchors] or None, cigar bytes [n * stride] or None, cigar lengths or None, status) tensors --
+        the side records with ``sides``, the gap scores with ``gap_scores`` --; ``out``: such a tuple to write into."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(t_start.numel())
+        total = int(anchor_t.numel())
+        dev = targets.device
+        if cigar_stride is None:
+            cigar_stride = _default_stride(max_tl, max_ql, binary_cigar)
+        if out is None:
+            rec = lambda: torch.empty((n, 8), dtype=torch.int32, device=dev)  # noqa: E731
+            out = (rec(), rec() if sides else None, rec() if sides else None, torch.empty(total, dtype=torch.int32, device=dev) if gap_scores else None,
+                   None if score_only else torch.empty(n * cigar_stride, dtype=torch.uint8, device=dev),
+                   None if score_only else torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+        aln, left, right, gs, cg, ln, st = out
+        p = SWParameters(*parameters)
+        flags = ((_lib.FLAG_BINARY_CIGAR if binary_cigar else 0) | (_lib.FLAG_SCORE_ONLY if score_only else 0) |
+                 (_lib.FLAG_EXTEND_TO_QUERY_END if to_query_end else 0) | (_lib.FLAG_EXTEND_ADAPTIVE_BAND if adaptive_band else 0))
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        rc = _lib.lib().mgl_sw_align_chain_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len),
+            ptr(anchor_start), ptr(anchor_t), ptr(anchor_q), ptr(anchor_len), total, int(max_tl), int(max_ql), int(max_gap_tl), int(max_gap_ql),
+            p.match, p.mismatch, p.gap_open, p.gap_extend, int(band), int(zdrop), ptr(aln), ptr(left), ptr(right), ptr(gs), ptr(cg), int(cigar_stride),
+            ptr(ln), ptr(st), flags)
         _check(rc, ctx)
         return out
 
