@@ -11,11 +11,14 @@
 //   pass 2  walks the path (sw.cpp:149-255).  The walk knows H of the cell it stands at, so a diagonal stretch up to the next
 //           kept row is CHECKED instead of recomputed: if H drops by exactly the sum of the stretch's substitution scores, every
 //           cell of it took the diagonal (PathWalk::verify_apply: the proof).  Only where that fails -- a gap, or a tie taken
-//           elsewhere: 0.4 blocks per pair on Illumina-style reads, 3.5 rounds per wave -- the lane recomputes the 16 x LANE_CK_COLS
-//           block the walk stands in: the SAME column code with the flags switched on, started from the block's kept row and
-//           checkpoint, so every flag is bit for bit the one the full fill would have stored, into a small private buffer; it walks
-//           as far as the block reaches and goes on.  Both pairs of a lane do this in lock step (one packed recomputation serves
-//           pair A's block and pair B's, different blocks in general).
+//           elsewhere -- the walk first checks the shorter stretch to the LEFT EDGE of its block where that comes before the
+//           kept row (the column checkpoints are kept columns: PathWalk::edge_len), so that a gap beyond the edge does not cost a
+//           block on this side of it.  Then -- 2.78 rounds per wave on Illumina-style reads, 3.50 before the edge check
+//           (docs/history.md C.000a) -- the lane recomputes the 16 x LANE_CK_COLS block the walk stands in: the SAME column
+//           code with the flags switched on, started from the block's kept row and checkpoint, so every flag is bit for bit the
+//           one the full fill would have stored, into a small private buffer; it walks as far as the block reaches and goes on.
+//           Both pairs of a lane do this in lock step (one packed recomputation serves pair A's block and pair B's, different
+//           blocks in general).
 //
 // Same arithmetic, same range guard (dp16_range_ok), same results as sw_dp16_lane_kernel.
 //
@@ -364,6 +367,43 @@ struct PathWalk {
             done = !(I > 0 && J > 0); // sw.cpp:214
         }
         return all && !done;
+    }
+    // ---- the kept COLUMN.  A stuck walk is about to have the block it stands in recomputed -- but the stretch that failed is up to
+    // 16 cells long and a block only CK columns wide: where the diagonal leaves the block through its left edge before it reaches the
+    // kept row, the gap may lie beyond that edge, the recomputed block holds nothing but diagonal moves, and the block behind the
+    // edge is recomputed for the same gap.  The left edge of block b is a kept column just as row 16 m is a kept row: pass 1's
+    // checkpoints hold H[row][CK b] of every row (h[r] of ck_strip's save(), what ck_block starts from), and the proof above holds
+    // for any end cell whose H is known.  So before the block round a stuck walk checks the stretch to the EDGE (I - Lc, CK b),
+    // Lc = J - CK b, where that is the nearer one (b >= 1: column 0 is a formula the row check knows; Lc < stretch_to(0): equal
+    // lengths end in the cell the row check has just failed).  If it adds up the walk takes it and stands at the right edge of
+    // block (k, b - 1) -- still stuck: the rest of the failed stretch, at most 15 cells, lies inside that block -- and the block
+    // round picks that block from (pi, pj) by itself.  The edge cell's row is >= 1 and in the walk's own 16-row band.
+    __device__ __forceinline__ int edge_len() const // 0: no such stretch
+    {
+        if (done || mode != 0 || !stuck) return 0;
+        const int lc = J - ((J - 1) & ~(CK - 1));
+        return J > CK && lc < stretch_to(0) ? lc : 0;
+    }
+    // H[I - lc][CK b] in stored form, both pairs of the lane (the indexing of ck_block's ia / ib)
+    __device__ __forceinline__ unsigned edge_load(const WaveMem &wm, int nb, int lc) const
+    {
+        const int r0 = I - lc - 1, b = (J - 1) / CK;
+        return WaveMem::at32<unsigned>(wm.cku, 4u * ((unsigned)((((r0 >> 5) * (nb - 1) + (b - 1)) * 64 + 2 * (r0 & (R - 1))) * 64) + wm.lane));
+    }
+    // (tw, qw: win_load() of the walk's cell.)  Returns true when the stretch was taken.
+    __device__ __forceinline__ bool edge_apply(const unsigned w, const unsigned (&tw)[5], const unsigned (&qw)[5], int lc, int half, const BlockGeom &g)
+    {
+        if (lc == 0) return false;
+        const int ie = I - lc, je = J - lc;
+        const int he = (half ? hi16(w) : lo16(w)) - (ie + je) * g.gext - g.base;
+        if (hc - he != lc * g.match + mismatches(tw, qw, lc, g.codes) * (g.mismatch - g.match)) return false;
+        take('M', lc);
+        I = ie;
+        J = je;
+        hc = he;
+        pi = I;
+        pj = J; // (I >= 1 and J = CK b >= CK: not done)
+        return true;
     }
     // overhangs, text, per-pair results (walk_and_write's tail + traceback_one_pair)
     // (rp: the pair's record where pass 1 left it in memory -- read back here, by the lane that wrote it, rather than carried in a dozen
@@ -750,7 +790,7 @@ __device__ __forceinline__ void lds_to_global(void *dst, const unsigned char *sr
 // but the kernel ran 2.5 ms per 10 M pairs SLOWER (65.2 against 62.6: the opaque lane number hides its range from the address
 // arithmetic of every store of pass 1) -- measured, scripts/ck_regs_probe.sh, and left alone.)
 template <bool VIA_LDS, bool FOLD>
-__device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbArgs &walk_in, const int64_t gw, const int64_t slot, const int lane, unsigned char *out_lds)
+__device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbArgs &walk_in, const int64_t gw, const int64_t slot, const int lane, unsigned char *out_lds, const bool first)
 {
     const int64_t n_ls = (a.count + 1) >> 1;
 #ifdef MGL_CK_PHASES
@@ -828,16 +868,22 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
                 stage_ascii<false, true>(a.q.data + a.q.off[pA], a.q.data + a.q.off[pB], ql, qblocks, qst);
             }
         }
-        // row 0 (the border row, sw.cpp:14-18,31-35) in stored form: H[0][j], E[1][j] = H[0][j] - o
-        for (int j = 0; j <= ql; ++j) {
-            const int hb0 = border(j, gopen, gext, indel) + j * gext + base;
-            const unsigned hp = pack2(hb0, hb0);
-            wm.bnd[(size_t)j * 64] = make_uint2(hp, pk_sub(hp, c.o_e));
-        }
-        // column 0 of the rows entering the other strips: H[32 k][0] (what a strip's first diagonal starts from)
-        for (int k = 1; k <= strips; ++k) {
-            const int hb0 = border(k * R, gopen, gext, indel) + k * R * gext + base;
-            wm.bnd[(size_t)k * (ql + 1) * 64] = make_uint2(pack2(hb0, hb0), 0u);
+        // The borders depend on the launch's geometry and parameters alone and nothing overwrites them (the strips write columns
+        // 1 .. ql of the rows they leave), so a wave of a launch with ONE geometry writes them in front of its first tile only
+        // (`first`) -- once per LAUNCH: the next launch on this region may have another geometry, strategy or gap cost.  A grouped
+        // launch's geometry changes from tile to tile.
+        if (grouped || first) {
+            // row 0 (the border row, sw.cpp:14-18,31-35) in stored form: H[0][j], E[1][j] = H[0][j] - o
+            for (int j = 0; j <= ql; ++j) {
+                const int hb0 = border(j, gopen, gext, indel) + j * gext + base;
+                const unsigned hp = pack2(hb0, hb0);
+                wm.bnd[(size_t)j * 64] = make_uint2(hp, pk_sub(hp, c.o_e));
+            }
+            // column 0 of the rows entering the other strips: H[32 k][0] (what a strip's first diagonal starts from)
+            for (int k = 1; k <= strips; ++k) {
+                const int hb0 = border(k * R, gopen, gext, indel) + k * R * gext + base;
+                wm.bnd[(size_t)k * (ql + 1) * 64] = make_uint2(pack2(hb0, hb0), 0u);
+            }
         }
     }
 
@@ -946,7 +992,38 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
                     wb.grid_load(wm, ql, gb);
                 }
                 const bool ma = wa.verify_apply(ta, qa, ga, 0, geom), mb = wb.verify_apply(tb, qb, gb, 1, geom);
+#ifdef MGL_CK_PHASES
+                if (lane == 0) atomicAdd(&mgl_ck_phase_ticks[12], 1ull);
+#endif
                 if (!__builtin_amdgcn_ballot_w64(ma || mb)) break;
+            }
+            // every walk that is stuck where it stands now: the stretch to its block's left edge, where that comes before the kept
+            // row (PathWalk::edge_len) -- one more dword and 16 bases of both sequences per walk, one memory latency per block round
+            {
+                const int ea = wa.edge_len(), eb = wb.edge_len();
+                if (__builtin_amdgcn_ballot_w64((ea | eb) != 0)) {
+                    unsigned ta[5], qa[5], tb[5], qb[5], ha = 0u, hb = 0u;
+                    if (ea) {
+                        wa.win_load(wm, 0, tblocks, qblocks, ta, qa);
+                        ha = wa.edge_load(wm, nb, ea);
+                    }
+                    if (eb) {
+                        wb.win_load(wm, 1, tblocks, qblocks, tb, qb);
+                        hb = wb.edge_load(wm, nb, eb);
+                    }
+                    const bool xa = wa.edge_apply(ha, ta, qa, ea, 0, geom), xb = wb.edge_apply(hb, tb, qb, eb, 1, geom);
+#ifdef MGL_CK_PHASES
+                    const unsigned long long took_ = __popcll(__builtin_amdgcn_ballot_w64(xa)) + __popcll(__builtin_amdgcn_ballot_w64(xb));
+                    const unsigned long long tried_ = __popcll(__builtin_amdgcn_ballot_w64(ea != 0)) + __popcll(__builtin_amdgcn_ballot_w64(eb != 0));
+                    if (lane == 0) {
+                        atomicAdd(&mgl_ck_phase_ticks[10], took_);
+                        atomicAdd(&mgl_ck_phase_ticks[11], tried_ - took_);
+                    }
+#else
+                    (void)xa;
+                    (void)xb;
+#endif
+                }
             }
             CK_PHASE(3); // stretches that add up
             if (__builtin_amdgcn_ballot_w64(!wa.done || !wb.done) == 0) break;
@@ -1108,7 +1185,7 @@ __device__ __forceinline__ void lane_ck_grid(const DpArgs &a, const TbArgs &walk
 #ifdef MGL_CK_TRACE
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
 #endif
-        sw_dp16_lane_ck_tile<VIA_LDS, FOLD>(a, walk, tile, slot, lane, out_lds);
+        sw_dp16_lane_ck_tile<VIA_LDS, FOLD>(a, walk, tile, slot, lane, out_lds, tile == slot); // (later tiles: slots + a draw)
 #ifdef MGL_CK_TRACE
         if (lane == 0 && tile < (1 << 17)) {
             unsigned hw;
@@ -1226,6 +1303,8 @@ extern "C" void mgl_ck_phases_dump()
     for (int k = 0; k < 8; ++k) tot += h[k];
     for (int k = 0; k < 8; ++k) fprintf(stderr, "phase %-20s %6.2f %%  %10.1f ticks per wave\n", names[k], 100.0 * h[k] / (double)tot, (double)h[k] / (double)h[9]);
     fprintf(stderr, "waves %llu, block rounds per wave %.2f\n", h[9], (double)h[8] / (double)h[9]);
+    fprintf(stderr, "edge stretches per wave: taken %.3f, tried and not adding up %.3f; verify iterations per wave %.2f\n", (double)h[10] / (double)h[9],
+            (double)h[11] / (double)h[9], (double)h[12] / (double)h[9]);
     memset(h, 0, sizeof h);
     hipMemcpyToSymbol(HIP_SYMBOL(mgl_ck_phase_ticks), h, sizeof h);
 }
