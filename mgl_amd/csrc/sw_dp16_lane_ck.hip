@@ -446,11 +446,52 @@ struct PathWalk {
     }
 };
 
+// ---- the last row (sw.cpp:116-127) as ONE running key per lane half.  The reference scans H[tl][1 .. ql] for the largest score, among
+// equal scores the smallest |tl - j|, among those the earlier column.  The last strip keeps that running best while it sweeps the
+// columns, so the row is neither stored nor read back:
+//   frame   a stored H[tl][j] is X + (tl + j) e + base (X the score).  w = stored + (ql - j) e = X + (tl + ql) e + base does not depend
+//           on the column, so two columns' w compare as their scores do.  Range: base = 32767 - match min(tl, ql) - e (tl + ql)
+//           (dp16_base) makes w = X + 32767 - match min(tl, ql), and X <= match min(i, j) <= match min(tl, ql): w <= 32767, no
+//           overflow; (ql - j) e >= 0 and every stored value of the matrix is >= -32768 (dp16_range_ok): w >= stored, no underflow.
+//           So the wrapping packed add is exact in both halves.
+//   pref    row_pref(j) = ql - 1 - (the number of columns the reference prefers to j at equal score): a wave-uniform number in
+//           [0, ql - 1], one value per column (the preference is a strict total order), larger = preferred.
+//   key     (w << 16) | pref as a signed 32-bit integer: the larger key is the column the reference keeps, two columns never have
+//           equal keys, and the winner's w and j are read back from it once, after the strip (row_col).
+// pref fits the key's low half for ql <= ROW_KEY_MAX_QL whatever tl is.  The kernel also accepts longer queries (gext = 0 leaves the
+// longer side of a pair unbounded, dp16_range_ok): those launches store the row and scan it after pass 1 as before (LAST_ROW_STORED).
+constexpr int ROW_KEY_MAX_QL = 65536;
+// columns of 1 .. ql that come before j in the reference's order at equal score: those strictly nearer to tl, and j's mirror image on
+// the left of tl where j lies on the right and the mirror is a column
+__device__ __forceinline__ int row_pref(const int tl, const int ql, const int j)
+{
+    const int d = abs(tl - j);
+    const int nearer = max(min(ql, tl + d - 1) - max(1, tl - d + 1) + 1, 0);
+    return ql - 1 - nearer - ((j > tl && tl - d >= 1) ? 1 : 0);
+}
+// the column whose row_pref is `pref`
+__device__ __forceinline__ int row_col(const int tl, const int ql, const int pref)
+{
+    const int r = ql - 1 - pref;
+    if (tl > ql) return ql - r; // every column lies left of tl: the nearest is the last
+    const int m = min(tl - 1, ql - tl); // distances 1 .. m have a column on either side of tl
+    if (r <= 2 * m) return (r & 1) ? tl - ((r + 1) >> 1) : tl + (r >> 1);
+    return tl - 1 > m ? tl - (r - m) : tl + (r - m); // the longer side alone
+}
+
+// what a strip is to the last row
+enum : int {
+    NOT_LAST = 0,
+    LAST_ROW_KEYS = 1,   // the last strip: the running keys above
+    LAST_ROW_STORED = 2, // the last strip of a launch with ql > ROW_KEY_MAX_QL: H[tl][j] goes to the carry row "entering strip `strips`"
+};
+
 // ---- pass 1: strip k, score only, keeping the rows and the column checkpoints
-template <bool LAST, int CODES>
+// (keyA / keyB: the last row's running keys; corner: H[tl][ql] of both halves in stored form -- the last strip only)
+template <int LAST, int CODES>
 __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql, const int nb, const WaveMem &wm, const unsigned *qst, const unsigned *tst,
                                          const LaneConsts &c, const int gopen, const int gext, const int base, const bool indel, int &bestA,
-                                         int &bestA_i, int &bestB, int &bestB_i)
+                                         int &bestA_i, int &bestB, int &bestB_i, int &keyA, int &keyB, unsigned &corner)
 {
     const int i0 = k * R;
     unsigned h[R], f[R], t[R];
@@ -478,6 +519,7 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
     unsigned *ckp = wm.ck + (size_t)k * (nb - 1) * 64 * 64;
     unsigned hd = bp[-64].x; // H[32 k][0]
     // column u (0 .. 3) of the group whose query dwords are qa / qb
+    int j = 1;
     auto one_column = [&](const uint2 top, const unsigned qa, const unsigned qb, const int u) {
         unsigned e = top.y;
         uint2 mid;
@@ -488,17 +530,24 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
         hd = top.x;
         if (!(MGL_CK_ABLATE & 4)) mp[0] = mid;
         mp += 64;
-        if (!LAST) {
+        if (LAST == NOT_LAST) {
             bo[0] = make_uint2(h[R - 1], e);
-        } else { // the row the last-row scan reads: H[tl][j]
+        } else { // H[tl][j]
             unsigned bot = h[R - 1];
             if (rl != R - 1) {
 #pragma unroll
                 for (int r = 0; r < R - 1; ++r) bot = (r == rl) ? h[r] : bot;
             }
-            bo[0] = make_uint2(bot, 0u);
+            if (LAST == LAST_ROW_STORED) {
+                bo[0] = make_uint2(bot, 0u);
+            } else { // (the frame constant and pref are wave-uniform: scalar arithmetic beside the column's packed instructions)
+                const int jc = j + u, lift = (ql - jc) * gext;
+                const unsigned w = pk_add(bot, pack2(lift, lift)), pref = (unsigned)row_pref(tl, ql, jc);
+                keyA = max(keyA, (int)((w << 16) | pref));
+                keyB = max(keyB, (int)((w & 0xffff0000u) | pref));
+            }
         }
-        bo += 64;
+        if (LAST != LAST_ROW_KEYS) bo += 64;
     };
     auto save = [&]() { // the state BEFORE column j: H[.][j-1] and the horizontal-gap values entering column j
 #pragma unroll
@@ -513,7 +562,6 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
     // in the same queue -- hides behind a thousand instructions of arithmetic instead of stalling the wave at every group (measured
     // before: a third of the waves' lifetime in s_waitcnt at two waves per SIMD).  Reads past column ql stay inside the wave's own
     // region (the next kept row follows) and are never used.
-    int j = 1;
     uint2 n0 = bp[0], n1 = bp[64], n2 = bp[128], n3 = bp[192];
     unsigned nqa = qst[0], nqb = qst[64];
     for (; j + 3 <= ql; j += 4) {
@@ -538,6 +586,13 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
         one_column(n0, nqa, nqb, 0);
         if (j + 1 <= ql) one_column(n1, nqa, nqb, 1);
         if (j + 2 <= ql) one_column(n2, nqa, nqb, 2);
+    }
+    if (LAST != NOT_LAST) { // H[tl][ql], where the walks of the non-softclip strategies start
+        corner = h[R - 1];
+        if (rl != R - 1) {
+#pragma unroll
+            for (int r = 0; r < R - 1; ++r) corner = (r == rl) ? h[r] : corner;
+        }
     }
     // last column (sw.cpp:100-104), as in sw_dp16_lane.hip
 #pragma unroll
@@ -890,19 +945,39 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
     CK_PHASE(0); // staging
     // ---- pass 1
     int bestA = NEG_INF, bestA_i = -1, bestB = NEG_INF, bestB_i = -1;
-    if (codes) {
-        for (int k = 0; k < strips - 1; ++k) ck_strip<false, CM>(k, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i);
-        ck_strip<true, CM>(strips - 1, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i);
-    } else {
-        for (int k = 0; k < strips - 1; ++k) ck_strip<false, CMP_BYTES>(k, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i);
-        ck_strip<true, CMP_BYTES>(strips - 1, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i);
-    }
+    int keyA = INT32_MIN, keyB = INT32_MIN; // the last row's running best (row_pref above): every column's key is >= this
+    unsigned corner = 0u;                   // H[tl][ql], stored form
+    const bool row_stored = ql > ROW_KEY_MAX_QL;
+#define CK_STRIPS(CMP)                                                                                                                      \
+    do {                                                                                                                                    \
+        for (int k = 0; k < strips - 1; ++k)                                                                                                \
+            ck_strip<NOT_LAST, CMP>(k, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i, keyA, keyB, corner); \
+        if (row_stored)                                                                                                                     \
+            ck_strip<LAST_ROW_STORED, CMP>(strips - 1, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i, keyA, keyB, corner); \
+        else                                                                                                                                \
+            ck_strip<LAST_ROW_KEYS, CMP>(strips - 1, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i, keyA, keyB, corner); \
+    } while (0)
+    if (codes)
+        CK_STRIPS(CM);
+    else
+        CK_STRIPS(CMP_BYTES);
+#undef CK_STRIPS
 
     CK_PHASE(1); // pass 1
-    // ---- last row (sw.cpp:116-127), as in sw_dp16_lane.hip: the last strip left H[tl][j] in the row "entering strip `strips`"
-    int rmA = NEG_INF, rdA = 0x7fffffff, rjA = 0x7fffffff, rmB = NEG_INF, rdB = 0x7fffffff, rjB = 0x7fffffff;
-    int cornerA = 0, cornerB = 0; // H[tl][ql]
-    {
+    // ---- last row (sw.cpp:116-127): the winner of each half out of its key
+    int rmA, rdA, rjA, rmB, rdB, rjB;
+    const int frame = (tl + ql) * gext + base; // w - frame = the score
+    const int cornerA = lo16(corner) - frame, cornerB = hi16(corner) - frame;
+    if (!row_stored) {
+        rjA = row_col(tl, ql, keyA & 0xffff);
+        rjB = row_col(tl, ql, keyB & 0xffff);
+        rmA = (keyA >> 16) - frame;
+        rmB = (keyB >> 16) - frame;
+        rdA = abs(tl - rjA);
+        rdB = abs(tl - rjB);
+    } else { // the last strip left H[tl][j] in the row "entering strip `strips`"
+        rmA = rmB = NEG_INF;
+        rdA = rjA = rdB = rjB = 0x7fffffff;
         const uint2 *const last = wm.bnd + (size_t)strips * (ql + 1) * 64;
         for (int j0 = 1; j0 <= ql; j0 += 8) { // eight columns' loads at once
             unsigned bots[8];
@@ -924,8 +999,6 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
                     rmB = tb_ ? sb : rmB;
                     rdB = tb_ ? d : rdB;
                     rjB = tb_ ? j : rjB;
-                    cornerA = sa; // (the last one stays: H[tl][ql])
-                    cornerB = sb;
                 }
             }
         }
@@ -948,7 +1021,7 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
         if (half ? validB : lvalid) a.rec[half ? slotB : slotA] = r;
     }
 
-    CK_PHASE(2); // last row, records
+    CK_PHASE(2); // records
     // ---- pass 2
     const int64_t pA = a.first + slotA, pB = a.first + slotB;
     // where the walks write: the caller's arrays, or (walk_in.coalesced_out) this tile's 128 slots of each in LDS -- cigar [128][stride] |
@@ -1298,7 +1371,7 @@ extern "C" void mgl_ck_phases_dump()
     unsigned long long h[16] = {0};
     hipDeviceSynchronize();
     hipMemcpyFromSymbol(h, HIP_SYMBOL(mgl_ck_phase_ticks), sizeof h);
-    static const char *names[8] = {"staging", "pass 1", "last row + records", "stretches", "block flags", "walk in block", "(loop exit)", "finish"};
+    static const char *names[8] = {"staging", "pass 1", "records", "stretches", "block flags", "walk in block", "(loop exit)", "finish"};
     unsigned long long tot = 0;
     for (int k = 0; k < 8; ++k) tot += h[k];
     for (int k = 0; k < 8; ++k) fprintf(stderr, "phase %-20s %6.2f %%  %10.1f ticks per wave\n", names[k], 100.0 * h[k] / (double)tot, (double)h[k] / (double)h[9]);
