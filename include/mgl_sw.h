@@ -700,6 +700,52 @@ int mgl_sw_align_chain_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
                                     int32_t *d_cigar_len_out, int32_t *d_status_out, int flags);
 
 /*
+ * ANCHOR CHAINING (NOT a reference function; opt-in): the chain stage in front of mgl_sw_align_chain_batch_device.  A read's seed hits
+ * -- candidates, many of them on a wrong diagonal or from repeats -- go in; the best colinear chain comes out, on the device, in the
+ * layout that entry reads.  Integers only; defined by tests/chain_dp_textbook.py.  Per read p: tl = d_t_len[p] and ql = d_q_len[p]
+ * (no sequence byte is read) and N_p >= 0 candidates: d_cand_start (int64, n + 1 entries, CSR into d_cand_t, d_cand_q, d_cand_len,
+ * int32 arrays of total_cand entries); candidate i lays T[t_i .. t_i + l_i) against Q[q_i .. q_i + l_i), the chain entry's convention.
+ * Per call: max_pred in 1 .. 64, max_dist_t, max_dist_q, bw >= 0, pen_gap, pen_skip >= 0 in 1/256 units.
+ * The DP is defined on INDEX order alone: the entry neither sorts nor checks an order.  Callers sort a read's candidates by target
+ * position, so that the window of max_pred predecessors means something.  j may precede i iff
+ *   i - max_pred <= j < i,  dt = t_i - (t_j + l_j) >= 0,  dq = q_i - (q_j + l_j) >= 0,  dt <= max_dist_t,  dq <= max_dist_q,
+ *   dd = |dt - dq| <= bw
+ * (no overlap: exactly the inequalities the chain entry demands of two consecutive anchors), and
+ *   f(i) = max( l_i, max_j f(j) + l_i - pen(j, i) ),  pen = ((pen_gap dd + pen_skip min(dt, dq)) >> 8) + (ilog2(dd + 1) >> 1),
+ * ilog2 = floor log2: minimap2's chaining score with its float terms made integer.  Ties go to the largest j, "no predecessor"
+ * counting as j = -1; pred(i) is that j, relative to the read's first candidate.  The chain ends in the i with the largest f(i), ties
+ * to the smallest i, follows pred to -1 and is emitted in ascending order, K_p anchors; its score is f(end).  f >= 1, and f is at most
+ * the sum of the chain's l, which is at most ql because every step has dq >= 0: f is an int32 for every ql.  N_p = 0: K_p = 0, score
+ * 0, status 0 (mgl_sw_align_chain_batch_device then refuses that pair for K < 1).
+ * Outputs, all device memory: d_chain_start_out (int64, n + 1 entries, ascending: the prefix sum of K_p, made on the device);
+ * d_chain_t_out, d_chain_q_out, d_chain_len_out (int32, capacity total_cand): read p's anchors from d_chain_start_out[p] on, nothing
+ * written at or beyond d_chain_start_out[n]; d_chain_score_out (int32, n); d_f_out, d_pred_out (optional, int32 per candidate): f and
+ * pred of every candidate of a read with status 0, for callers who trace other chains themselves.  With total_anchors = total_cand,
+ * max_gap_tl = max_dist_t and max_gap_ql = max_dist_q these arrays are valid arguments of mgl_sw_align_chain_batch_device as they are.
+ * The call fails before any device work with MGL_SW_ERR_BAD_ARG on a null required array, n or total_cand outside [0, 2^30],
+ * max_pred outside 1 .. 64, a negative distance, bw or penalty, max_cand < 0, and
+ * pen_gap bw + pen_skip min(max_dist_t, max_dist_q) >= 2^31 (the int32 guard of pen); with MGL_SW_ERR_DEVICE without a GPU.
+ * d_status_out (optional), per read, in this order: MGL_SW_ERR_BAD_ARG for a range of d_cand_start that descends or leaves
+ * [0, total_cand), tl or ql below 1, a candidate with l < 1, t < 0, q < 0, t + l > tl or q + l > ql; MGL_SW_ERR_UNSUPPORTED for
+ * N_p > max_cand, the caller's bound, which sizes what the kernel keeps per read (one byte per candidate: in LDS up to 32768, in a
+ * workspace slot per wave beyond).  A refused read gets K_p = 0, score 0 and nothing else written.  Ranges that overlap (possible only
+ * around a descending one) are the caller's error: the reads that share candidates get unspecified chains, nothing is written out of
+ * bounds.
+ * Device work, all on `stream`, no synchronisation: sw_chain_dp_kernel (one wave per read, persistent: the checks, the DP, the
+ * trace-back), sw_chain_dp_scan_kernel (d_chain_start_out) and sw_chain_dp_pack_kernel (the chains into their CSR place).  The
+ * workspace -- 4 bytes per read, 4 per candidate, and the slots -- comes out of one borrowing of the context's and counts against
+ * its limit: MGL_SW_ERR_NOMEM where the limit does not hold it beside one slot.  This stage has no MGL_SW_KERNEL_* id:
+ * mgl_sw_ctx_get_timing's fill_kernel stays what it was (the other fields are reset as by every device entry).
+ * LIMITS: max_pred <= 64; overlapping hits on one diagonal are not chained to each other (minimap2 trims them); one chain per read
+ * (d_f_out / d_pred_out are the way to others); no max_skip heuristic; candidates are not sorted here.
+ */
+int mgl_sw_chain_anchors_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const int32_t *d_t_len, const int32_t *d_q_len,
+                                      const int64_t *d_cand_start, const int32_t *d_cand_t, const int32_t *d_cand_q, const int32_t *d_cand_len,
+                                      int64_t total_cand, int max_cand, int max_pred, int max_dist_t, int max_dist_q, int bw, int pen_gap, int pen_skip,
+                                      int64_t *d_chain_start_out, int32_t *d_chain_t_out, int32_t *d_chain_q_out, int32_t *d_chain_len_out,
+                                      int32_t *d_chain_score_out, int32_t *d_f_out, int32_t *d_pred_out, int32_t *d_status_out);
+
+/*
  * Logical backtrack matrix of one pair, the reference's calculateMatrix
  * (sw_scalar.h:7 / sw.cpp:5-146): btr is (tl+1)*(ql+1) int32 row-major with
  * row 0 / column 0 zero, +k = k rows up (deletion run), -k = k columns left

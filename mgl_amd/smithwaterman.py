@@ -38,6 +38,7 @@ BatchResult = namedtuple("BatchResult", "offsets scores cigars cigar_len")
 ExtendResult = namedtuple("ExtendResult", "score t_end q_end score_qend t_end_qend rows_done dropped cigar_from cigars cigar_len")
 SeedExtendResult = namedtuple("SeedExtendResult", "score t_beg t_end q_beg q_end seed_score dropped cigar_from cigars cigar_len")
 ChainAlignResult = namedtuple("ChainAlignResult", "score t_beg t_end q_beg q_end anchor_score dropped cigar_from cigars cigar_len")
+ChainAnchorsResult = namedtuple("ChainAnchorsResult", "chains score status")
 
 
 class CigarColumn:
@@ -397,6 +398,75 @@ class MicrosoftSmithWaterman:
             ptr(ln), ptr(st), flags)
         _check(rc, ctx)
         return out
+
+    def chain_anchors(self, t_lens, q_lens, candidates, max_pred=64, max_dist=5000, bw=500, pen_gap=38, pen_skip=0, max_cand=None, return_dp=False):
+        """mgl_sw_chain_anchors_batch_device over lists: ``candidates[k]`` = a list of (t, q, l) for read k -- t_lens[k] and q_lens[k]
+        are its window's and its query's length --, sorted by the caller (by target position) if the window of ``max_pred`` predecessors
+        is to mean something.  ``max_dist``: one bound or (max_dist_t, max_dist_q).  The colinear chaining DP of
+        tests/chain_dp_textbook.py and the best chain of every read.  NOT a reference function.  Returns ChainAnchorsResult: ``chains``
+        (a list of lists of (t, q, l)), ``score`` and ``status`` arrays (a refused read has an empty chain; no exception for a read's
+        status); with ``return_dp`` also f and pred of every candidate (int32 arrays in the order of the lists; what a refused read's
+        candidates hold is unspecified): (result, f, pred)."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        n = len(candidates)
+        assert len(t_lens) == len(q_lens) == n
+        start = np.zeros(n + 1, np.int64)
+        if n:
+            np.cumsum([len(c) for c in candidates], out=start[1:])
+        flat = np.asarray([a for c in candidates for a in c], dtype=np.int32).reshape(-1, 3)
+        if max_cand is None:
+            max_cand = int(np.diff(start).max(initial=0))
+        g = lambda x, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dt))).to(dev)  # noqa: E731
+        out = self.chain_anchors_device(g(t_lens, np.int32), g(q_lens, np.int32), g(start, np.int64), g(flat[:, 0], np.int32), g(flat[:, 1], np.int32),
+                                        g(flat[:, 2], np.int32), max_cand, max_pred, max_dist, bw, pen_gap, pen_skip, dp=return_dp)
+        torch.cuda.synchronize(dev)
+        cs, ct, cq, cl, score, f, pred, st = (None if x is None else x.cpu().numpy() for x in out)
+        chains = [[(int(ct[i]), int(cq[i]), int(cl[i])) for i in range(cs[k], cs[k + 1])] for k in range(n)]
+        res = ChainAnchorsResult(chains, score, st)
+        return (res, f, pred) if return_dp else res
+
+    def chain_anchors_device(self, t_len, q_len, cand_start, cand_t, cand_q, cand_len, max_cand, max_pred=64, max_dist=5000, bw=500, pen_gap=38,
+                             pen_skip=0, out=None, dp=False):
+        """The device-tensor form: torch tensors on this context's GPU (int32 lengths and candidates, int64 ``cand_start`` [n + 1]);
+        enqueued on the current stream, not synchronised.  Returns (chain_start [n + 1] int64, chain_t, chain_q, chain_len [candidates],
+        score [n], f or None, pred or None [candidates], status [n]) tensors -- f and pred with ``dp`` --; ``out``: such a tuple to
+        write into.  The first four are ``align_chain_device``'s anchor arguments as they are."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(t_len.numel())
+        total = int(cand_t.numel())
+        dev = t_len.device
+        i32 = lambda k: torch.empty(k, dtype=torch.int32, device=dev)  # noqa: E731
+        if out is None:
+            out = (torch.empty(n + 1, dtype=torch.int64, device=dev), i32(total), i32(total), i32(total), i32(n), i32(total) if dp else None,
+                   i32(total) if dp else None, i32(n))
+        cs, ct, cq, cl, score, f, pred, st = out
+        dist_t, dist_q = (max_dist, max_dist) if np.isscalar(max_dist) else max_dist
+        spare = torch.empty(2, dtype=torch.int64, device=dev) if n == 0 or total == 0 else None  # an empty tensor has no address: the entry wants one
+        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        rc = _lib.lib().mgl_sw_chain_anchors_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(t_len), ptr(q_len), ptr(cand_start), ptr(cand_t), ptr(cand_q), ptr(cand_len), total,
+            int(max_cand), int(max_pred), int(dist_t), int(dist_q), int(bw), int(pen_gap), int(pen_skip), ptr(cs), ptr(ct), ptr(cq), ptr(cl), ptr(score),
+            ptr(f), ptr(pred), ptr(st))
+        _check(rc, ctx)
+        return out
+
+    def align_candidates_device(self, targets, t_start, t_len, queries, q_start, q_len, cand_start, cand_t, cand_q, cand_len, max_tl, max_ql, max_cand,
+                                band, zdrop, parameters=GATK_PARAMETERS, max_pred=64, max_dist=5000, bw=500, pen_gap=38, pen_skip=0, chain_out=None,
+                                **align):
+        """Candidates -> chain -> alignment on the current stream: ``chain_anchors_device`` and then ``align_chain_device`` on the
+        tensors it wrote (max_gap = max_dist), nothing read back and nothing synchronised in between.  ``align``: the further
+        arguments of ``align_chain_device``.  Returns (the chain stage's tuple, the alignment's tuple).  A read with no candidates or
+        a refused one has K = 0 and is status MGL_SW_ERR_BAD_ARG in the alignment's tuple.  ``max_dist`` is also the gap bound of the
+        alignment, which stages a CIGAR row of 4 (max_dist_t + max_dist_q) bytes per candidate: keep it near the largest gap expected."""
+        chain = self.chain_anchors_device(t_len, q_len, cand_start, cand_t, cand_q, cand_len, max_cand, max_pred, max_dist, bw, pen_gap, pen_skip,
+                                          out=chain_out)
+        dist_t, dist_q = (max_dist, max_dist) if np.isscalar(max_dist) else max_dist
+        return chain, self.align_chain_device(targets, t_start, t_len, queries, q_start, q_len, *chain[:4], max_tl, max_ql, dist_t, dist_q, band, zdrop,
+                                              parameters, **align)
 
     def align_packed_2bit(self, target_bases, target_base_count, t_start, t_len, query_bases, query_base_count, q_start, q_len,
                           max_tl, max_ql, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,

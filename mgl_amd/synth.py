@@ -87,3 +87,81 @@ def ont_pair(rng, length, sub=0.05, ins=0.05, dele=0.05):
         out.append(c)
     q = BASES[np.asarray(out, dtype=np.int64)]
     return t, q
+
+
+def chain_flank(rng, length, every=200, anchor=20, jumps=5, jump=30):
+    """One flank of a long-read pair with known anchors (DESIGN.md section 9f's pairs): a random target of ``length`` and a noisy copy
+    -- 5 % substitutions, 1 % + 1 % indels of 1 .. 3 bases, ``jumps`` insertions of ``jump`` bases -- in which about every ``every``
+    target bases ``anchor`` bases are copied exactly.  -> (t, q, [(start in t, start in q)] of the exact stretches), t and q bytes."""
+    t = BASES[rng.integers(4, size=length)]
+    at = {(length // (jumps + 1)) * (x + 1) + 11 * x for x in range(jumps)}
+    q, skip, exact, marks, pending = [], 0, 0, [], False
+    for pos, ch in enumerate(t):
+        pending = pending or pos in at
+        if pending and not exact:  # (a jump that falls into an exact stretch comes behind it)
+            q.extend(BASES[rng.integers(4, size=jump)])
+            pending = False
+        if pos % every == every // 2 and pos + anchor <= length and not skip:
+            exact = anchor
+            marks.append((pos, len(q)))
+        if exact:
+            exact -= 1
+            q.append(ch)
+            continue
+        if skip:
+            skip -= 1
+            continue
+        r = rng.random()
+        if r < 0.01:
+            skip = int(rng.integers(0, 3))
+            continue
+        if r < 0.02:
+            q.extend(BASES[rng.integers(4, size=int(rng.integers(1, 4)))])
+        q.append(BASES[rng.integers(4)] if rng.random() < 0.05 else ch)
+    return t.tobytes(), np.array(q, np.uint8).tobytes(), marks
+
+
+def chain_pairs(seed, count, length=10000, seed_len=50, every=200, anchor=20, jumps=5, jump=30):
+    """``count`` pairs of about ``length`` bases with their true chains: two flanks of ``chain_flank`` laid outwards from an exact seed
+    of ``seed_len`` bases near the middle.  -> [(T, Q, chain)], chain = [(t, q, l)] ascending, every anchor exact."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(count):
+        left_len = (length - seed_len) // 2 + int(rng.integers(-(length // 50), length // 50 + 1))
+        (lt, lq, lm), (rt, rq, rm) = (chain_flank(rng, n, every, anchor, jumps, jump) for n in (left_len, length - seed_len - left_len))
+        mid = BASES[rng.integers(4, size=seed_len)].tobytes()
+        # the left flank was made outwards from the seed and is laid down reversed: a stretch at (u, v) lies at (len - u - anchor, ...)
+        chain = sorted((len(lt) - u - anchor, len(lq) - v - anchor, anchor) for u, v in lm)
+        chain.append((len(lt), len(lq), seed_len))
+        chain += [(len(lt) + seed_len + u, len(lq) + seed_len + v, anchor) for u, v in rm]
+        T, Q = lt[::-1] + mid + rt, lq[::-1] + mid + rq
+        assert all(T[a:a + n] == Q[b:b + n] for a, b, n in chain)
+        out.append((T, Q, chain))
+    return out
+
+
+CAND_TRUE, CAND_OVERLAP, CAND_DECOY, CAND_REPEAT = range(4)
+
+
+def noisy_candidates(rng, tl, ql, chain, decoys=2.0, repeats=0.5, overlaps=0.5, off=(300, 3000)):
+    """What a seeding stage hands a chainer for one pair, given the pair's true ``chain``: the true anchors; per true anchor about
+    ``overlaps`` shorter hits inside it, shifted along the true diagonal (they overlap it); about ``repeats`` copies of it at the same
+    query position and another target position; and about ``decoys`` hits of its length on a wrong diagonal next to it.  A decoy or a
+    repeat copy is ``off[0]`` .. ``off[1]`` bases off the diagonal of the true anchor it was made from, to either side (at minimap2's
+    pen_gap = 38 / 256 a detour over a hit 300 off costs 48 each way and gains the hit's 20).  Sorted by
+    target position (then query position).  -> (candidates [(t, q, l)], kind per candidate: CAND_*)."""
+    out = [(t, q, l, CAND_TRUE) for t, q, l in chain]
+    for t, q, l in chain:
+        for _ in range(rng.poisson(overlaps)):
+            if l >= 4:
+                d = int(rng.integers(1, l // 2 + 1))
+                out.append((t + d, q + d, l - d, CAND_OVERLAP))
+        for kind, rate in ((CAND_REPEAT, repeats), (CAND_DECOY, decoys)):
+            for _ in range(rng.poisson(rate)):
+                shift = int(rng.integers(off[0], off[1] + 1)) * (1 if rng.random() < 0.5 else -1)
+                along = 0 if kind == CAND_REPEAT else int(rng.integers(-100, 101))  # a decoy lies anywhere around the anchor
+                nt, nq = t + along + shift, q + along
+                if 0 <= nt and nt + l <= tl and 0 <= nq and nq + l <= ql:
+                    out.append((nt, nq, l, kind))
+    out.sort()
+    return [c[:3] for c in out], [c[3] for c in out]
