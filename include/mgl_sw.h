@@ -746,6 +746,46 @@ int mgl_sw_chain_anchors_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
                                       int32_t *d_chain_score_out, int32_t *d_f_out, int32_t *d_pred_out, int32_t *d_status_out);
 
 /*
+ * SEEDING (NOT a reference function; opt-in): the seed stage in front of mgl_sw_chain_anchors_batch_device.  Reads and their windows go
+ * in; every pair's candidate anchors come out, on the device, in the CSR layout and the order that entry reads.  A read is seeded
+ * against its OWN window -- no index.  Integers only; defined by tests/seed_textbook.py.  Per pair p: the window T (tl = d_t_len[p]
+ * bytes from d_targets + d_t_start[p]) and the query Q (ql = d_q_len[p] bytes from d_queries + d_q_start[p]), ASCII.  Per call: k in
+ * 4 .. 16, w in 1 .. 32, max_occ in 1 .. 64, merge 0 / 1, max_cand in 1 .. 8192, cand_capacity in 0 .. 2^30.
+ * k-mers: A = 0, C = 1, G = 2, T = 3, upper case only; the k-mer at position i is valid iff all of its k bytes are one of these; its key
+ * is the 2k-bit number with the first base in the top bits; h = fmix32(key ^ 0x9E3779B9), murmur3's 32-bit finaliser.
+ * The sketch of a sequence of L bytes, nk = L - k + 1 positions (empty for nk < 1): the windows are [a, a + w) for a = 0 .. nk - w, the one
+ * window [0, nk) if nk < w; a window selects its valid position with the smallest h, ties to the smallest position, nothing if none is
+ * valid; the sketch is the set of selected positions.
+ * Hits: with occ(x) the number of positions of Q's sketch with key x, every position t of T's sketch with key x and 1 <= occ(x) <= max_occ
+ * gives one raw hit (t, q, k) per position q of Q's sketch with key x; R_p is their number.
+ * Merge (merge = 1): raw hits on one diagonal t - q are joined while the next starts at or before the end of the run so far (overlapping
+ * or touching); a run is the candidate (t0, q0, t_last + k - t0) -- the maximal diagonal runs of the cells the raw hits cover, each an
+ * exact match.  merge = 0: the candidates are the raw hits.  A pair's N_p candidates are ascending by (t, q), strictly.
+ * d_status_out (optional), per pair, the first that applies: MGL_SW_ERR_BAD_ARG for tl < 1 or ql < 1; MGL_SW_ERR_UNSUPPORTED for a query
+ * sketch of more than 8192 positions or R_p > max_cand (the bound is on the RAW hits: what the kernel holds and sorts);
+ * MGL_SW_ERR_NOMEM by the capacity rule: with S_p the sum of N_j over j < p (a refused pair counts 0), pairs are kept in index order while
+ * S_p + N_p <= cand_capacity, and from the first pair P* that does not fit on every pair, empty ones included, is MGL_SW_ERR_NOMEM (one
+ * refused above keeps that status).  A pair with a non-zero status has N_p = 0.
+ * Outputs, all device memory: d_cand_start_out (int64, n + 1 entries): S_p for p <= P*, S_(P*) beyond it -- ascending, and
+ * d_cand_start_out[n] <= cand_capacity; d_cand_t_out, d_cand_q_out, d_cand_len_out (int32, capacity cand_capacity): nothing is written
+ * at or beyond d_cand_start_out[n].  With total_cand = cand_capacity the four arrays are valid arguments of
+ * mgl_sw_chain_anchors_batch_device as they are.
+ * The call fails before any device work with MGL_SW_ERR_BAD_ARG on n outside [0, 2^30], a null required array or a parameter outside its
+ * range above; with MGL_SW_ERR_DEVICE without a GPU; with MGL_SW_ERR_NOMEM where the workspace limit does not hold the batch's staging
+ * (4 + 12 max_cand bytes per pair: the batch is staged whole) beside one slot (64 KiB, 160 KiB where max_cand is above 2048).
+ * Device work, all on `stream`, no synchronisation: sw_seed_kernel (one workgroup per pair, persistent: both sketches, the probe, the
+ * merge), sw_seed_scan_kernel (d_cand_start_out and the capacity cut) and sw_seed_pack_kernel (the candidates into their CSR place), out
+ * of one borrowing of the context's workspace.  This stage has no MGL_SW_KERNEL_* id: mgl_sw_ctx_get_timing's fill_kernel stays what it
+ * was (the other fields are reset as by every device entry).
+ * LIMITS: forward strand only; the pair's own window, no index; k <= 16; a query's sketch and a pair's raw hits are bounded at 8192; no
+ * occurrence cap on the window's side; the batch is staged whole.
+ */
+int mgl_sw_seed_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets, const int64_t *d_t_start, const int32_t *d_t_len,
+                             const uint8_t *d_queries, const int64_t *d_q_start, const int32_t *d_q_len, int k, int w, int max_occ, int merge,
+                             int max_cand, int64_t cand_capacity, int64_t *d_cand_start_out, int32_t *d_cand_t_out, int32_t *d_cand_q_out,
+                             int32_t *d_cand_len_out, int32_t *d_status_out);
+
+/*
  * Logical backtrack matrix of one pair, the reference's calculateMatrix
  * (sw_scalar.h:7 / sw.cpp:5-146): btr is (tl+1)*(ql+1) int32 row-major with
  * row 0 / column 0 zero, +k = k rows up (deletion run), -k = k columns left

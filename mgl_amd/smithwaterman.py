@@ -39,6 +39,7 @@ ExtendResult = namedtuple("ExtendResult", "score t_end q_end score_qend t_end_qe
 SeedExtendResult = namedtuple("SeedExtendResult", "score t_beg t_end q_beg q_end seed_score dropped cigar_from cigars cigar_len")
 ChainAlignResult = namedtuple("ChainAlignResult", "score t_beg t_end q_beg q_end anchor_score dropped cigar_from cigars cigar_len")
 ChainAnchorsResult = namedtuple("ChainAnchorsResult", "chains score status")
+SeedResult = namedtuple("SeedResult", "candidates status")
 
 
 class CigarColumn:
@@ -467,6 +468,61 @@ class MicrosoftSmithWaterman:
         dist_t, dist_q = (max_dist, max_dist) if np.isscalar(max_dist) else max_dist
         return chain, self.align_chain_device(targets, t_start, t_len, queries, q_start, q_len, *chain[:4], max_tl, max_ql, dist_t, dist_q, band, zdrop,
                                               parameters, **align)
+
+    def seed(self, targets, queries, k=15, w=10, max_occ=8, merge=True, max_cand=4096):
+        """mgl_sw_seed_batch_device over lists of byte strings: read k (``queries[k]``) is seeded against its own window
+        (``targets[k]``) -- the (w, k) minimizers of both, their common keys as hits, a key that occurs more than ``max_occ`` times in
+        the read's sketch dropped, and with ``merge`` the hits on one diagonal that overlap or touch merged into maximal exact runs
+        (tests/seed_textbook.py).  NOT a reference function.  ``max_cand`` bounds a pair's raw hits.  Returns SeedResult:
+        ``candidates`` (a list of lists of (t, q, l), ascending by (t, q): what ``chain_anchors`` takes) and ``status`` (a refused pair
+        has no candidates; no exception for a pair's status)."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        n, packed, _ = _pack_pairs(targets, queries, dev, 16, False)
+        out = self.seed_device(*packed[:6], k, w, max_occ, merge, max_cand)
+        torch.cuda.synchronize(dev)
+        cs, ct, cq, cl, st = (x.cpu().numpy() for x in out)
+        return SeedResult([[(int(ct[i]), int(cq[i]), int(cl[i])) for i in range(cs[p], cs[p + 1])] for p in range(n)], st)
+
+    def seed_device(self, targets, t_start, t_len, queries, q_start, q_len, k=15, w=10, max_occ=8, merge=True, max_cand=4096, cand_capacity=None,
+                    out=None):
+        """The device-tensor form: torch tensors on this context's GPU (uint8 bytes, int64 starts, int32 lengths); enqueued on the
+        current stream, not synchronised.  Returns (cand_start [n + 1] int64, cand_t, cand_q, cand_len [cand_capacity] int32, status
+        [n]) tensors; ``out``: such a tuple to write into (its status may be None), whose candidate arrays then give the capacity.
+        ``cand_capacity`` defaults to n * max_cand, which always fits; pairs from the first that does not fit on are status
+        MGL_SW_ERR_NOMEM.  The first four are ``chain_anchors_device``'s candidate arguments as they are."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(t_start.numel())
+        dev = targets.device
+        if cand_capacity is None:
+            cand_capacity = int(out[1].numel()) if out is not None else min(n * int(max_cand), 1 << 30)
+        if out is None:
+            i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
+            out = (torch.empty(n + 1, dtype=torch.int64, device=dev), i32(cand_capacity), i32(cand_capacity), i32(cand_capacity), i32(n))
+        cs, ct, cq, cl, st = out
+        assert min(ct.numel(), cq.numel(), cl.numel()) >= cand_capacity and cs.numel() >= n + 1
+        spare = torch.empty(2, dtype=torch.int64, device=dev) if n == 0 or cand_capacity == 0 else None  # an empty tensor has no address: the entry wants one
+        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        rc = _lib.lib().mgl_sw_seed_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len), int(k),
+            int(w), int(max_occ), int(merge), int(max_cand), int(cand_capacity), ptr(cs), ptr(ct), ptr(cq), ptr(cl), ptr(st))
+        _check(rc, ctx)
+        return out
+
+    def align_reads_device(self, targets, t_start, t_len, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters=GATK_PARAMETERS, k=15,
+                           w=10, max_occ=8, merge=True, max_cand=4096, cand_capacity=None, seed_out=None, **chain_align):
+        """Reads -> seeds -> chain -> alignment on the current stream: ``seed_device`` and then ``align_candidates_device`` on the
+        tensors it wrote, nothing read back and nothing synchronised in between.  ``chain_align``: the further arguments of
+        ``align_candidates_device`` (the chaining parameters, ``chain_out`` and those of ``align_chain_device``).  Returns (the seed
+        stage's tuple, the chain stage's tuple, the alignment's tuple).  A pair the seed stage refused or found nothing for has no
+        chain and is status MGL_SW_ERR_BAD_ARG in the alignment's tuple."""
+        seeds = self.seed_device(targets, t_start, t_len, queries, q_start, q_len, k, w, max_occ, merge, max_cand, cand_capacity, out=seed_out)
+        chain, aln = self.align_candidates_device(targets, t_start, t_len, queries, q_start, q_len, *seeds[:4], max_tl, max_ql, max_cand, band, zdrop,
+                                                  parameters, **chain_align)
+        return seeds, chain, aln
 
     def align_packed_2bit(self, target_bases, target_base_count, t_start, t_len, query_bases, query_base_count, q_start, q_len,
                           max_tl, max_ql, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,
