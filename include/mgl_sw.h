@@ -777,13 +777,66 @@ int mgl_sw_chain_anchors_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
  * merge), sw_seed_scan_kernel (d_cand_start_out and the capacity cut) and sw_seed_pack_kernel (the candidates into their CSR place), out
  * of one borrowing of the context's workspace.  This stage has no MGL_SW_KERNEL_* id: mgl_sw_ctx_get_timing's fill_kernel stays what it
  * was (the other fields are reset as by every device entry).
- * LIMITS: forward strand only; the pair's own window, no index; k <= 16; a query's sketch and a pair's raw hits are bounded at 8192; no
+ * LIMITS: forward strand only (both: mgl_sw_seed_strands_batch_device below); the pair's own window, no index; k <= 16; a query's sketch and a pair's raw hits are bounded at 8192; no
  * occurrence cap on the window's side; the batch is staged whole.
  */
 int mgl_sw_seed_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets, const int64_t *d_t_start, const int32_t *d_t_len,
                              const uint8_t *d_queries, const int64_t *d_q_start, const int32_t *d_q_len, int k, int w, int max_occ, int merge,
                              int max_cand, int64_t cand_capacity, int64_t *d_cand_start_out, int32_t *d_cand_t_out, int32_t *d_cand_q_out,
                              int32_t *d_cand_len_out, int32_t *d_status_out);
+
+/*
+ * SEEDING BOTH STRANDS (NOT a reference function; opt-in): mgl_sw_seed_batch_device for reads of unknown orientation.  Defined by
+ * tests/strand_textbook.py: the result is mgl_sw_seed_batch_device's on the batch of 2n ROWS, row 2p = (T_p, Q_p) and row 2p + 1 =
+ * (T_p, rc(Q_p)), with rc(Q)[i] = comp(Q[ql - 1 - i]); comp swaps upper-case A <-> T and C <-> G and maps every other byte to itself, so
+ * a k-mer that is not valid stays so at its mirrored place.  Statuses, the max_cand and 8192-sketch bounds and the capacity rule are
+ * per row and in row order; a candidate's q is a coordinate of that row's ORIENTED read.  Row 2p is what mgl_sw_seed_batch_device
+ * gives for pair p.  The arguments are that entry's, with n in [0, 2^29].
+ * Outputs, all device memory: d_cand_start_out (int64, 2n + 1 entries); d_cand_t_out, d_cand_q_out, d_cand_len_out (int32, capacity
+ * cand_capacity): nothing is written at or beyond d_cand_start_out[2n]; d_row_t_len_out, d_row_q_len_out (optional, int32, 2n entries
+ * each): tl_p and ql_p per row, so that with total_cand = cand_capacity these arrays are valid arguments of
+ * mgl_sw_chain_anchors_batch_device over 2n reads as they are; d_status_out (optional, 2n entries).
+ * The call fails before any device work as mgl_sw_seed_batch_device does; MGL_SW_ERR_NOMEM where the workspace limit does not hold the
+ * staging of the 2n rows (4 + 12 max_cand bytes per row) beside one slot (128 KiB, 320 KiB where max_cand is above 2048).
+ * Device work, all on `stream`, no synchronisation: sw_seed_strands_kernel (one workgroup per pair, persistent: the read sketched in both
+ * orientations from its bytes in place, the window read and sketched ONCE and probed against both, the merge per row), then
+ * sw_seed_scan_kernel and sw_seed_pack_kernel over the 2n rows, out of one borrowing of the context's workspace.  No MGL_SW_KERNEL_*
+ * id: mgl_sw_ctx_get_timing's fill_kernel stays what it was.
+ * LIMITS: those of mgl_sw_seed_batch_device but the strand; the staging doubles.
+ */
+int mgl_sw_seed_strands_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets, const int64_t *d_t_start,
+                                     const int32_t *d_t_len, const uint8_t *d_queries, const int64_t *d_q_start, const int32_t *d_q_len, int k, int w,
+                                     int max_occ, int merge, int max_cand, int64_t cand_capacity, int64_t *d_cand_start_out, int32_t *d_cand_t_out,
+                                     int32_t *d_cand_q_out, int32_t *d_cand_len_out, int32_t *d_row_t_len_out, int32_t *d_row_q_len_out,
+                                     int32_t *d_status_out);
+
+/*
+ * THE STRAND OF A READ (NOT a reference function; opt-in): between mgl_sw_chain_anchors_batch_device over the 2n rows of
+ * mgl_sw_seed_strands_batch_device and mgl_sw_align_chain_batch_device.  Defined by tests/strand_textbook.py (select_strand).  In: the
+ * n reads (d_queries, d_q_start, d_q_len; query_bytes is the size of d_queries and of d_queries_out) and the chain stage's outputs over
+ * the 2n rows: d_chain_start (int64, 2n + 1), d_chain_t, d_chain_q, d_chain_len (int32, total_chain entries, in [0, 2^30]),
+ * d_chain_score (int32, 2n).  Row r has K_r = d_chain_start[r + 1] - d_chain_start[r] anchors and the score c_r = d_chain_score[r], 0
+ * where K_r = 0.  strand_p = 1 iff c_(2p+1) > c_(2p): ties and two zeros give strand 0.  Pair p gets the K_p anchors of row
+ * 2p + strand_p and the oriented read, Q_p or rc(Q_p).
+ * Outputs, all device memory: d_strand_out (int32, n); d_queries_out (uint8, query_bytes; it must not overlap d_queries): read p
+ * oriented, at the SAME offset d_q_start[p], so that d_q_start and d_q_len serve both buffers -- no byte outside a read is written;
+ * d_anchor_start_out (int64, n + 1: the prefix sum of K_p, made on the device); d_anchor_t_out, d_anchor_q_out, d_anchor_len_out (int32,
+ * capacity total_chain): nothing is written at or beyond d_anchor_start_out[n] -- valid arguments of mgl_sw_align_chain_batch_device
+ * as they are; d_score_out (optional, int32, n: the chosen chain's score); d_status_out (optional, int32, n).
+ * Per pair MGL_SW_ERR_BAD_ARG for ql < 1, a read that leaves [0, query_bytes) or a row's range of d_chain_start that descends or leaves
+ * [0, total_chain]: strand 0, K_p = 0, score 0, and neither a byte nor an anchor is written for it.  Reads that overlap in d_queries,
+ * or row ranges that overlap, are the caller's error: the result is unspecified, nothing is written out of bounds.
+ * The call fails before any device work with MGL_SW_ERR_BAD_ARG on a null required array, n outside [0, 2^29], total_chain outside
+ * [0, 2^30] or query_bytes < 0; with MGL_SW_ERR_DEVICE without a GPU.
+ * Device work, all on `stream`, no synchronisation: sw_select_strand_kernel, sw_select_strand_scan_kernel, sw_select_strand_pack_kernel;
+ * the workspace is 4 bytes per pair.  No MGL_SW_KERNEL_* id.
+ * LIMITS: the choice is by chain score alone; one chain per read.
+ */
+int mgl_sw_select_strand_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_queries, const int64_t *d_q_start,
+                                      const int32_t *d_q_len, const int64_t *d_chain_start, const int32_t *d_chain_t, const int32_t *d_chain_q,
+                                      const int32_t *d_chain_len, const int32_t *d_chain_score, int64_t total_chain, int64_t query_bytes,
+                                      int32_t *d_strand_out, uint8_t *d_queries_out, int64_t *d_anchor_start_out, int32_t *d_anchor_t_out,
+                                      int32_t *d_anchor_q_out, int32_t *d_anchor_len_out, int32_t *d_score_out, int32_t *d_status_out);
 
 /*
  * Logical backtrack matrix of one pair, the reference's calculateMatrix

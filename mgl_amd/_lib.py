@@ -34,7 +34,8 @@ SYMBOLS = (
     "mgl_sw_align_batch_2bit", "mgl_sw_register_host_buffer", "mgl_sw_unregister_host_buffer", "mgl_sw_explain",
     "mgl_sw_explain_sized", "mgl_sw_ctx_check", "mgl_sw_local_batch_device_matrix", "mgl_sw_align_batch_device_banded",
     "mgl_sw_extend_batch_device", "mgl_sw_extend_seed_batch_device", "mgl_sw_align_chain_batch_device",
-    "mgl_sw_chain_anchors_batch_device", "mgl_sw_seed_batch_device",
+    "mgl_sw_chain_anchors_batch_device", "mgl_sw_seed_batch_device", "mgl_sw_seed_strands_batch_device",
+    "mgl_sw_select_strand_batch_device",
 )
 # MGL_SW_VERSION of the include/mgl_sw.h this mirror was written against: the structs below (Plan, Timing) are that header's, and the
 # library writes sizeof(ITS struct) through the pointers it is given -- so a library of another version is refused at load time
@@ -185,6 +186,8 @@ def lib():
         vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]
     L.mgl_sw_chain_anchors_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int64] + [C.c_int] * 7 + [vp] * 8
     L.mgl_sw_seed_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp] + [C.c_int] * 5 + [C.c_int64] + [vp] * 5
+    L.mgl_sw_seed_strands_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp] + [C.c_int] * 5 + [C.c_int64] + [vp] * 7
+    L.mgl_sw_select_strand_batch_device.argtypes = [vp, vp, C.c_int64] + [vp] * 8 + [C.c_int64] * 2 + [vp] * 8
     L.mgl_sw_backtrack_matrix.argtypes = [cp, C.c_int, cp, C.c_int] + [C.c_int] * 5 + [i32p, C.POINTER(Score)]
     L.mgl_sw_cigar_from_backtrack.argtypes = [i32p, C.c_int, C.c_int, C.c_int, C.POINTER(Score), cp, C.c_int,
                                               C.POINTER(C.c_int), C.POINTER(C.c_int)]

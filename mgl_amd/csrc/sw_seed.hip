@@ -19,7 +19,7 @@
 //
 // sw_seed_scan_kernel: one block, the exclusive prefix sum of the counts into d_cand_start_out with a running carry, 1024 pairs a step,
 // cut at the capacity.  sw_seed_pack_kernel: one wave per pair, the staging into the pair's CSR place.
-#include "sw_seed.h"
+#include "sw_seed_dev.h"
 
 namespace mgl_sw_dev {
 
@@ -40,18 +40,6 @@ struct SeedLds {
 };
 static_assert(sizeof(SeedLds) <= 64 * 1024, "a workgroup's LDS");
 __shared__ SeedLds s; // sw_seed_kernel's alone: the other two kernels reach nothing that names it
-
-__device__ inline uint32_t seed_hash(uint32_t key)
-{
-    uint32_t h = key ^ 0x9E3779B9u;
-    h ^= h >> 16;
-    h *= 0x85EBCA6Bu;
-    h ^= h >> 13;
-    h *= 0xC2B2AE35u;
-    return h ^ (h >> 16);
-}
-
-__device__ inline uint8_t seed_code(uint8_t b) { return b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : b == 'T' ? 3 : 4; }
 
 // the exclusive prefix sum of v over the workgroup, and the sum
 __device__ inline int seed_block_scan(const int v, int &total)
@@ -119,36 +107,6 @@ __device__ __noinline__ int64_t seed_sketch_block(const uint8_t *seq, const int6
     }
     __syncthreads();
     return lo;
-}
-
-// a[0 .. n2), n2 a power of two, ascending; `val` (or null) moves with its key
-__device__ __noinline__ void seed_bitonic(uint64_t *a, uint32_t *val, const int n2)
-{
-    for (int size = 2; size <= n2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int i = threadIdx.x; i < n2 / 2; i += SEED_THREADS) {
-                const int l = 2 * i - (i & (stride - 1)), h = l + stride;
-                const bool asc = (l & size) == 0;
-                const uint64_t x = a[l], y = a[h];
-                if ((x > y) == asc) {
-                    a[l] = y;
-                    a[h] = x;
-                    if (val) {
-                        const uint32_t vx = val[l];
-                        val[l] = val[h];
-                        val[h] = vx;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-}
-
-__device__ inline int seed_pow2(const int n)
-{
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
 }
 
 __global__ __launch_bounds__(SEED_THREADS) void sw_seed_kernel(const SeedStageArgs a)

@@ -524,6 +524,94 @@ class MicrosoftSmithWaterman:
                                                   parameters, **chain_align)
         return seeds, chain, aln
 
+    def seed_strands(self, targets, queries, k=15, w=10, max_occ=8, merge=True, max_cand=4096):
+        """mgl_sw_seed_strands_batch_device over lists of byte strings: ``seed`` for reads of unknown orientation
+        (tests/strand_textbook.py).  Pair p gives two rows: row 2p is ``seed``'s result for (targets[p], queries[p]), row 2p + 1 that
+        for (targets[p], the reverse complement of queries[p]) -- a candidate's q is a coordinate of that row's oriented read.  NOT a
+        reference function.  Returns SeedResult over the 2n rows."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        n, packed, _ = _pack_pairs(targets, queries, dev, 16, False)
+        out = self.seed_strands_device(*packed[:6], k, w, max_occ, merge, max_cand)
+        torch.cuda.synchronize(dev)
+        cs, ct, cq, cl, _, _, st = (x.cpu().numpy() for x in out)
+        return SeedResult([[(int(ct[i]), int(cq[i]), int(cl[i])) for i in range(cs[r], cs[r + 1])] for r in range(2 * n)], st)
+
+    def seed_strands_device(self, targets, t_start, t_len, queries, q_start, q_len, k=15, w=10, max_occ=8, merge=True, max_cand=4096,
+                            cand_capacity=None, out=None):
+        """The device-tensor form: ``seed_device``'s arguments; enqueued on the current stream, not synchronised.  Returns (cand_start
+        [2n + 1] int64, cand_t, cand_q, cand_len [cand_capacity] int32, row_t_len, row_q_len, status [2n] int32) tensors over the 2n
+        rows; ``out``: such a tuple to write into (its last three may be None), whose candidate arrays then give the capacity.
+        ``cand_capacity`` defaults to 2n * max_cand, which always fits.  (row_t_len, row_q_len) and the first four are
+        ``chain_anchors_device``'s arguments over the 2n rows as they are."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(t_start.numel())
+        dev = targets.device
+        if cand_capacity is None:
+            cand_capacity = int(out[1].numel()) if out is not None else min(2 * n * int(max_cand), 1 << 30)
+        if out is None:
+            i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
+            out = (torch.empty(2 * n + 1, dtype=torch.int64, device=dev), i32(cand_capacity), i32(cand_capacity), i32(cand_capacity), i32(2 * n),
+                   i32(2 * n), i32(2 * n))
+        cs, ct, cq, cl, rt, rq, st = out
+        assert min(ct.numel(), cq.numel(), cl.numel()) >= cand_capacity and cs.numel() >= 2 * n + 1
+        assert all(x is None or x.numel() >= 2 * n for x in (rt, rq, st))
+        spare = torch.empty(2, dtype=torch.int64, device=dev) if n == 0 or cand_capacity == 0 else None  # an empty tensor has no address: the entry wants one
+        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        rc = _lib.lib().mgl_sw_seed_strands_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len), int(k),
+            int(w), int(max_occ), int(merge), int(max_cand), int(cand_capacity), ptr(cs), ptr(ct), ptr(cq), ptr(cl), ptr(rt), ptr(rq), ptr(st))
+        _check(rc, ctx)
+        return out
+
+    def select_strand_device(self, queries, q_start, q_len, chain_start, chain_t, chain_q, chain_len, chain_score, out=None):
+        """mgl_sw_select_strand_batch_device on device tensors: the n reads and ``chain_anchors_device``'s first five outputs over the 2n
+        rows of ``seed_strands_device``; enqueued on the current stream, not synchronised.  Read p's strand is 1 iff the chain of row
+        2p + 1 scores higher than that of row 2p (tests/strand_textbook.py).  Returns (strand [n] int32, queries_out uint8 (as large as
+        ``queries``: read p oriented at q_start[p]; bytes outside the reads are not written), anchor_start [n + 1] int64, anchor_t,
+        anchor_q, anchor_len [as chain_t] int32, score [n], status [n]) tensors; ``out``: such a tuple to write into (its last two may
+        be None).  With queries_out for the queries, the four anchor arrays are ``align_chain_device``'s arguments as they are."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(q_start.numel())
+        total = int(chain_t.numel())
+        dev = queries.device
+        if out is None:
+            i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
+            out = (i32(n), torch.empty_like(queries), torch.empty(n + 1, dtype=torch.int64, device=dev), i32(total), i32(total), i32(total), i32(n), i32(n))
+        strand, qo, as_, at, aq, al, score, st = out
+        assert chain_start.numel() >= 2 * n + 1 and chain_score.numel() >= 2 * n and min(chain_q.numel(), chain_len.numel()) >= total
+        assert qo.numel() >= queries.numel() and as_.numel() >= n + 1 and min(at.numel(), aq.numel(), al.numel()) >= total and strand.numel() >= n
+        spare = torch.empty(2, dtype=torch.int64, device=dev)  # an empty tensor has no address: the entry wants one
+        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        rc = _lib.lib().mgl_sw_select_strand_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(queries), ptr(q_start), ptr(q_len), ptr(chain_start), ptr(chain_t), ptr(chain_q),
+            ptr(chain_len), ptr(chain_score), total, int(queries.numel()), ptr(strand), ptr(qo), ptr(as_), ptr(at), ptr(aq), ptr(al), ptr(score), ptr(st))
+        _check(rc, ctx)
+        return out
+
+    def align_reads_strands_device(self, targets, t_start, t_len, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters=GATK_PARAMETERS,
+                                   k=15, w=10, max_occ=8, merge=True, max_cand=4096, cand_capacity=None, seed_out=None, max_pred=64, max_dist=5000,
+                                   bw=500, pen_gap=38, pen_skip=0, chain_out=None, select_out=None, **align):
+        """``align_reads_device`` for reads of unknown orientation, on the current stream: ``seed_strands_device`` ->
+        ``chain_anchors_device`` over the 2n rows -> ``select_strand_device`` -> ``align_chain_device`` on the oriented reads, nothing
+        read back and nothing synchronised in between.  ``align``: the further arguments of ``align_chain_device``.  Returns (the seed
+        stage's tuple, the chain stage's tuple, the choice's tuple, the alignment's tuple).  q_beg / q_end and the CIGAR of the alignment
+        are in the ORIENTED read's coordinates (the choice's queries_out): on the read as given, a pair of strand 1 spans
+        [ql - q_end, ql - q_beg).  A pair with a chain on neither row is strand 0 and status MGL_SW_ERR_BAD_ARG in the alignment's
+        tuple."""
+        seeds = self.seed_strands_device(targets, t_start, t_len, queries, q_start, q_len, k, w, max_occ, merge, max_cand, cand_capacity, out=seed_out)
+        chain = self.chain_anchors_device(seeds[4], seeds[5], *seeds[:4], max_cand, max_pred, max_dist, bw, pen_gap, pen_skip, out=chain_out)
+        chosen = self.select_strand_device(queries, q_start, q_len, *chain[:5], out=select_out)
+        dist_t, dist_q = (max_dist, max_dist) if np.isscalar(max_dist) else max_dist
+        aln = self.align_chain_device(targets, t_start, t_len, chosen[1], q_start, q_len, *chosen[2:6], max_tl, max_ql, dist_t, dist_q, band, zdrop,
+                                      parameters, **align)
+        return seeds, chain, chosen, aln
+
     def align_packed_2bit(self, target_bases, target_base_count, t_start, t_len, query_bases, query_base_count, q_start, q_len,
                           max_tl, max_ql, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,
                           out=None):

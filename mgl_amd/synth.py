@@ -140,6 +140,16 @@ def chain_pairs(seed, count, length=10000, seed_len=50, every=200, anchor=20, ju
     return out
 
 
+_COMP = np.arange(256, dtype=np.uint8)
+_COMP[[65, 67, 71, 84]] = [84, 71, 67, 65]
+
+
+def revcomp(b):
+    """The reverse complement of a byte string as the strand stages define it (tests/strand_textbook.py): upper-case A <-> T and
+    C <-> G, every other byte kept, the order reversed."""
+    return _COMP[np.frombuffer(bytes(b), np.uint8)][::-1].tobytes()
+
+
 CAND_TRUE, CAND_OVERLAP, CAND_DECOY, CAND_REPEAT = range(4)
 
 
