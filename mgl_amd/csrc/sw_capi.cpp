@@ -1140,6 +1140,10 @@ int run_device(mgl_sw_ctx *ctx, hipStream_t stream, int64_t n, const SeqSet &tse
             da.fold_k = P.fold.k;
             da.fold_bm = P.fold.bm;
             da.fold_bx = P.fold.bx;
+            {
+                const char *const wse = getenv("MGL_SW_DEBUG_WALK_STAGED"); // (1: the checkpointed lane kernel's walks read the staged sequences for ASCII input too; read per call: the tests run both forms)
+                da.walk_staged = wse && atoi(wse) != 0 ? 1 : 0;
+            }
             da.lane_slots = 0;
             da.tile_ctr = nullptr;
             da.grid_fault = nullptr;

@@ -88,6 +88,9 @@ struct DpArgs {
     // sw_dp16_lane_ck_kernel and the strip kernels without stored flags: the folded diagonal of their base-code form (diag_fold below;
     // fold_k = 0: none, or MGL_SW_DEBUG_DIAG_FOLD=0), which selects their *_fold twins
     int fold_k, fold_bm, fold_bx;
+    // sw_dp16_lane_ck_kernel, ASCII input: pass 2's walks compare the bases of the wave's staged copies, as they do for 2-bit input, instead
+    // of the caller's own arrays (MGL_SW_DEBUG_WALK_STAGED=1: the tests compare both forms)
+    int walk_staged;
 };
 
 struct TbArgs {

@@ -30,6 +30,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "sw_device.h"
 #include "sw_lane_cell.h"
 #include "sw_traceback.h"
@@ -75,9 +77,59 @@ __device__ __forceinline__ unsigned lo_hi(unsigned a, unsigned b) { return __bui
 
 // what pass 2 needs to know about the wave's geometry and scoring
 struct BlockGeom {
-    int ql, nb, match, mismatch, gopen, gext, base;
+    int tl, ql, nb, match, mismatch, gopen, gext, base;
     bool indel;
-    bool codes; // the staged sequences hold base codes
+    bool codes;  // the walks' windows hold base codes (the staged sequences do, and the walks read those)
+    bool direct; // the walks' windows come from the caller's arrays (SeqBlocks): raw bytes
+};
+
+// ---- a pair's sequence where the CALLER keeps it (ASCII input), as pass 2's walks read it: whole aligned 16-byte blocks, the same
+// bytes the reference compares (sw.cpp:55) whatever the wave staged.  A walk's window is 64 (16) consecutive bases that end at the
+// cell it stands at: at most five (two) blocks, one load instruction each -- the staged copy is [4-base block][A | B][lane], every
+// dword of a window a load of its own that uses 4 bytes of each 64-byte sector it touches (17 + 17 per pair against 5 + 5).
+// Block 0 is the block that holds the sequence's first byte, block `last` the one that holds its last: an index outside 0 .. last
+// is clamped (SeqWords::word does the same for dwords), so every block that is loaded holds at least one byte of the pair's own
+// sequence and no load leaves the pages the caller's bytes lie in, wherever in a block the sequence starts and ends.  What a clamped
+// block puts into the window are bytes in front of the sequence (never counted: a stretch is at most min(I, J) cells long) or behind
+// the window's last base (shifted out).
+struct SeqBlocks {
+    const uint4 *base; // block 0
+    int lo;            // where in block 0 the sequence's first byte stands
+    __device__ __forceinline__ void init(const uint8_t *p)
+    {
+        lo = (int)(reinterpret_cast<uintptr_t>(p) & 15);
+        base = reinterpret_cast<const uint4 *>(p - lo); // (pointer arithmetic, not a rounded integer: the loads stay global loads)
+    }
+    // bases end - W .. end - 1 (0-based; 1 <= end <= len) as W / 4 + 1 dwords that start at the window's first base rounded down to
+    // a dword: the window's dword k is alignbyte(w[k + 1], w[k], return value), the form the staged windows have.  The funnel shift
+    // by the low four bits of the window's address is two rounds of selects for its dword part (by 2, by 1); the byte part is the
+    // alignbyte the compare does anyway.
+    template <int W>
+    __device__ __forceinline__ unsigned window(const int end, const int len, unsigned (&w)[W / 4 + 1]) const
+    {
+        const int w0 = lo + end - W; // the window's first byte counted from block 0's first (negative: in front of the sequence)
+        const int b0 = w0 >> 4, last = max(lo + len - 1, 0) >> 4;
+        const unsigned s = (unsigned)w0 & 15u;
+        unsigned d[W / 4 + 4];
+#pragma unroll
+        for (int g = 0; g <= W / 16; ++g) {
+            // (the byte offset in 32 bits, as WaveMem::at32)
+            const uint4 v = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(base) + 16u * (unsigned)min(max(b0 + g, 0), last));
+            d[4 * g] = v.x;
+            d[4 * g + 1] = v.y;
+            d[4 * g + 2] = v.z;
+            d[4 * g + 3] = v.w;
+        }
+        // (bit selects, v_bfi_b32, not ?: -- two loads of d[] behind a condition become ONE load at a selected address while d[] is
+        // still an array in memory, and then it stays one: the window went through scratch, 80 accesses per verify iteration)
+        const unsigned by2 = 0u - ((s >> 3) & 1u), by1 = 0u - ((s >> 2) & 1u);
+        unsigned e[W / 4 + 2];
+#pragma unroll
+        for (int k = 0; k < W / 4 + 2; ++k) e[k] = (d[k + 2] & by2) | (d[k] & ~by2);
+#pragma unroll
+        for (int k = 0; k < W / 4 + 1; ++k) w[k] = (e[k + 1] & by1) | (e[k] & ~by1);
+        return s & 3u;
+    }
 };
 
 // the wave's arrays (every pointer includes the lane): what pass 1 keeps, time-major -- a lane only ever reads what it wrote itself
@@ -109,6 +161,9 @@ struct WaveMem {
 // ---- pass 2: the walk of one pair (calculateCigar, sw.cpp:149-255) as a machine that can stop at a block's edge and go on in
 // the next block.  (pi, pj) is the cell whose flags it needs next: the current cell, or the cell a gap run is counting through
 // (TbView::vrun / hrun taken apart).
+struct WinShift { // what alignbyte takes for the dwords of a walk's two windows (PathWalk::win_load, win64_load)
+    unsigned t, q;
+};
 struct PathWalk {
     int I, J, pi, pj, n, seg;
     int hc;     // mode 0: H[I][J], the score of the cell the walk stands at
@@ -116,6 +171,7 @@ struct PathWalk {
     char state;
     bool done;
     bool stuck; // the stretch above (I, J) does not add up: the walk needs this block's flags
+    SeqBlocks ts, qs; // BlockGeom::direct: the pair's target and query in the caller's arrays
     CigarWriter cw;
 
     __device__ __forceinline__ void take(char next, int step)
@@ -186,17 +242,17 @@ struct PathWalk {
     }
     // returns false when the walk cannot go on inside this block (finished, or the cell it needs next is in another block)
     // (tw, qw: win_load() of the cell the walk stands at -- mode 0 only: the scores of the diagonal steps it takes)
-    __device__ __forceinline__ bool apply(const unsigned (&w)[LOOK], const unsigned (&tw)[5], const unsigned (&qw)[5], int half, int k, int b,
-                                          const BlockGeom &g)
+    __device__ __forceinline__ bool apply(const unsigned (&w)[LOOK], const unsigned (&tw)[5], const unsigned (&qw)[5], const WinShift sh, int half,
+                                          int k, int b, const BlockGeom &g)
     {
         char op = 0; // the CIGAR element this round completes, if any: taken in ONE place (take() is a large piece of code)
         int len = 0;
-        const bool more = moves(w, tw, qw, half, k, b, g, op, len);
+        const bool more = moves(w, tw, qw, sh, half, k, b, g, op, len);
         if (len > 0) take(op, len);
         return more;
     }
-    __device__ __forceinline__ bool moves(const unsigned (&w)[LOOK], const unsigned (&tw)[5], const unsigned (&qw)[5], int half, int k, int b,
-                                          const BlockGeom &g, char &op, int &len)
+    __device__ __forceinline__ bool moves(const unsigned (&w)[LOOK], const unsigned (&tw)[5], const unsigned (&qw)[5], const WinShift sh, int half,
+                                          int k, int b, const BlockGeom &g, char &op, int &len)
     {
         if (done) return false;
         if (mode == 1 && pi < 1) { // the run reached the matrix's top (TbView::vrun: r >= 1)
@@ -228,7 +284,7 @@ struct PathWalk {
             }
             if (mode == 0) {
                 if (cnt > 0) {
-                    hc -= cnt * g.match + mismatches(tw, qw, cnt, g.codes) * (g.mismatch - g.match);
+                    hc -= cnt * g.match + mismatches(tw, qw, sh, cnt, g.codes) * (g.mismatch - g.match);
                     op = 'M';
                     len = cnt;
                     I -= cnt;
@@ -279,28 +335,39 @@ struct PathWalk {
     // at most 16 bases of both sequences (their staged copies: [4-base block][A | B][lane] dwords).  Only where the sum does NOT
     // fit -- a gap, or a tie taken elsewhere -- does the walk need the flags of the block.
     __device__ __forceinline__ bool can_verify() const { return !done && mode == 0 && !stuck; }
-    // bases I - 16 .. I - 1 (0-based) of the target and J - 16 .. J - 1 of the query: byte 15 of the window belongs to cell (I, J)
-    __device__ __forceinline__ void win_load(const WaveMem &wm, int half, int tblocks, int qblocks, unsigned (&tw)[5], unsigned (&qw)[5]) const
+    // bases I - 16 .. I - 1 (0-based) of the target and J - 16 .. J - 1 of the query: byte 15 of the window belongs to cell (I, J).
+    // Returns what alignbyte takes to bring dwords k, k + 1 of either window to its bases 4 k .. 4 k + 3.  g.direct (wave-uniform,
+    // one value per launch): out of the caller's arrays, two 16-byte loads per sequence -- else the staged dwords, five per sequence.
+    __device__ __forceinline__ WinShift win_load(const WaveMem &wm, int half, int tblocks, int qblocks, const BlockGeom &g, unsigned (&tw)[5], unsigned (&qw)[5]) const
     {
+        WinShift sh;
+        if (g.direct) {
+            sh.t = ts.window<16>(I, g.tl, tw);
+            sh.q = qs.window<16>(J, g.ql, qw);
+            return sh;
+        }
         const int dt = (I - 16) >> 2, dq = (J - 16) >> 2;
 #pragma unroll
         for (int k = 0; k < 5; ++k) { // (blocks before the sequence: block 0 again -- those bytes are never counted)
             tw[k] = wm.tblock(min(max(dt + k, 0), tblocks - 1), half);
             qw[k] = wm.qblock(min(max(dq + k, 0), qblocks - 1), half);
         }
+        sh.t = (unsigned)(I - 16) & 3u;
+        sh.q = (unsigned)(J - 16) & 3u;
+        return sh;
     }
     // how many of the cells (I, J), (I-1, J-1) .. (I-L+1, J-L+1) hold different bases (raw byte compare, sw.cpp:55); L <= 16, I, J
-    // (codes: the staged target holds codes 0 .. 3, the staged query 8 x code or 32 -- sw_lane_cell.h)
-    __device__ __forceinline__ int mismatches(const unsigned (&tw)[5], const unsigned (&qw)[5], int L, bool codes) const
+    // (codes: the staged target holds codes 0 .. 3, the staged query 8 x code or 32 -- sw_lane_cell.h; sh: win_load()'s)
+    __device__ __forceinline__ int mismatches(const unsigned (&tw)[5], const unsigned (&qw)[5], const WinShift sh, int L, bool codes) const
     {
-        const unsigned st = (unsigned)(I - 16) & 3u, sq = (unsigned)(J - 16) & 3u;
-        const int drop = 16 - L, dq = drop >> 2, sh = (drop & 3) * 8; // the window's low `drop` bytes are not part of the stretch
+        const unsigned st = sh.t, sq = sh.q;
+        const int drop = 16 - L, dq = drop >> 2, cut = (drop & 3) * 8; // the window's low `drop` bytes are not part of the stretch
         int n = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const unsigned tt = __builtin_amdgcn_alignbyte(tw[k + 1], tw[k], st);
             const unsigned nz = nonzero_bytes((codes ? tt << 3 : tt) ^ __builtin_amdgcn_alignbyte(qw[k + 1], qw[k], sq));
-            n += __popc(k > dq ? nz : k == dq ? nz >> sh : 0u);
+            n += __popc(k > dq ? nz : k == dq ? nz >> cut : 0u);
         }
         return n;
     }
@@ -308,14 +375,24 @@ struct PathWalk {
     // sequences and the VB rows' H are fetched together, their addresses depend on nothing the round computes -- and takes the
     // longest one that adds up (if the stretch to a row adds up, so does the stretch to every row before it).
     static constexpr int VB = 4;
-    __device__ __forceinline__ void win64_load(const WaveMem &wm, int half, int tblocks, int qblocks, unsigned (&tw)[17], unsigned (&qw)[17]) const
+    // (g.direct: five 16-byte loads per sequence out of the caller's arrays; else seventeen staged dwords)
+    __device__ __forceinline__ WinShift win64_load(const WaveMem &wm, int half, int tblocks, int qblocks, const BlockGeom &g, unsigned (&tw)[17], unsigned (&qw)[17]) const
     {
+        WinShift sh;
+        if (g.direct) {
+            sh.t = ts.window<64>(I, g.tl, tw);
+            sh.q = qs.window<64>(J, g.ql, qw);
+            return sh;
+        }
         const int dt = (I - 64) >> 2, dq = (J - 64) >> 2;
 #pragma unroll
         for (int k = 0; k < 17; ++k) {
             tw[k] = wm.tblock(min(max(dt + k, 0), tblocks - 1), half);
             qw[k] = wm.qblock(min(max(dq + k, 0), qblocks - 1), half);
         }
+        sh.t = (unsigned)(I - 64) & 3u;
+        sh.q = (unsigned)(J - 64) & 3u;
+        return sh;
     }
     // the stretch to the m-th kept row above the walk's cell (m = 0: the next one), cut where the diagonal leaves the matrix
     __device__ __forceinline__ int stretch_to(int m) const { return min(I - max((((I - 1) >> 4) - m) << 4, 0), J); }
@@ -329,11 +406,12 @@ struct PathWalk {
         }
     }
     // returns true when all VB stretches were taken and the walk can try the next ones
-    __device__ __forceinline__ bool verify_apply(const unsigned (&tw)[17], const unsigned (&qw)[17], const unsigned (&w)[VB], int half, const BlockGeom &g)
+    __device__ __forceinline__ bool verify_apply(const unsigned (&tw)[17], const unsigned (&qw)[17], const WinShift sh, const unsigned (&w)[VB], int half,
+                                                 const BlockGeom &g)
     {
         if (!can_verify()) return false;
         // bit u of `differ`: the bases of cell (I - u, J - u) differ (byte 63 - u of the window)
-        const unsigned st = (unsigned)(I - 64) & 3u, sq = (unsigned)(J - 64) & 3u;
+        const unsigned st = sh.t, sq = sh.q;
         unsigned long long differ = 0;
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
@@ -390,13 +468,14 @@ struct PathWalk {
         const int r0 = I - lc - 1, b = (J - 1) / CK;
         return WaveMem::at32<unsigned>(wm.cku, 4u * ((unsigned)((((r0 >> 5) * (nb - 1) + (b - 1)) * 64 + 2 * (r0 & (R - 1))) * 64) + wm.lane));
     }
-    // (tw, qw: win_load() of the walk's cell.)  Returns true when the stretch was taken.
-    __device__ __forceinline__ bool edge_apply(const unsigned w, const unsigned (&tw)[5], const unsigned (&qw)[5], int lc, int half, const BlockGeom &g)
+    // (tw, qw, sh: win_load() of the walk's cell.)  Returns true when the stretch was taken.
+    __device__ __forceinline__ bool edge_apply(const unsigned w, const unsigned (&tw)[5], const unsigned (&qw)[5], const WinShift sh, int lc, int half,
+                                               const BlockGeom &g)
     {
         if (lc == 0) return false;
         const int ie = I - lc, je = J - lc;
         const int he = (half ? hi16(w) : lo16(w)) - (ie + je) * g.gext - g.base;
-        if (hc - he != lc * g.match + mismatches(tw, qw, lc, g.codes) * (g.mismatch - g.match)) return false;
+        if (hc - he != lc * g.match + mismatches(tw, qw, sh, lc, g.codes) * (g.mismatch - g.match)) return false;
         take('M', lc);
         I = ie;
         J = je;
@@ -1040,7 +1119,19 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
     PathWalk wa, wb;
     wa.start(walk, rec[0], oA, tl, ql, lvalid, cornerA);
     wb.start(walk, rec[1], oB, tl, ql, validB, cornerB);
-    BlockGeom geom;
+    // Where the walks take the bases they compare.  ASCII input: from the caller's own arrays, in 16-byte loads (SeqBlocks) -- raw
+    // bytes, which is what the reference compares, whatever form the wave staged.  2-bit input (and a.walk_staged): from the staged
+    // dwords.  One value per launch, wave-uniform, fixed here in front of the loops; both forms are plain global loads.
+    const bool direct = !a.t.packed2 && !a.walk_staged;
+    if (direct) { // (an invalid half walks nothing: it holds the lane's pair A, or the launch's last pair)
+        wa.ts.init(a.t.data + a.t.off[pA]);
+        wa.qs.init(a.q.data + a.q.off[pA]);
+        wb.ts.init(a.t.data + a.t.off[pB]);
+        wb.qs.init(a.q.data + a.q.off[pB]);
+    }
+    BlockGeom geom_launch;
+    BlockGeom &geom = geom_launch;
+    geom.tl = tl;
     geom.ql = ql;
     geom.nb = nb;
     geom.match = match;
@@ -1050,54 +1141,90 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
     geom.base = base;
     geom.indel = indel;
     geom.codes = codes;
+    geom.direct = false;
     const bool by_score = !(MGL_CK_ABLATE & 8);
     const int tblocks = strips * (R / 4), qblocks = (ql + 3) >> 2;
+    // The two loops of pass 2 that read windows, once per form: in either copy the form is a constant, so it holds the loads, the
+    // registers and the compare of its own form only (both forms behind a run-time branch at every load: 80 scratch accesses in the
+    // verify loop).  The block's recomputation between them reads the staged codes and exists once.
+    auto stretches = [&](auto direct_form) __attribute__((always_inline)) {
+        BlockGeom geom = geom_launch;
+        geom.direct = decltype(direct_form)::value;
+        geom.codes = !decltype(direct_form)::value && codes;
+        for (;;) { // every walk standing at a cell takes the diagonal stretches whose scores add up (PathWalk::verify_apply)
+            unsigned ta[17], qa[17], tb[17], qb[17], ga[PathWalk::VB], gb[PathWalk::VB];
+            WinShift sa = {0u, 0u}, sb = {0u, 0u};
+            if (wa.can_verify()) {
+                sa = wa.win64_load(wm, 0, tblocks, qblocks, geom, ta, qa);
+                wa.grid_load(wm, ql, ga);
+            }
+            if (wb.can_verify()) {
+                sb = wb.win64_load(wm, 1, tblocks, qblocks, geom, tb, qb);
+                wb.grid_load(wm, ql, gb);
+            }
+            const bool ma = wa.verify_apply(ta, qa, sa, ga, 0, geom), mb = wb.verify_apply(tb, qb, sb, gb, 1, geom);
+#ifdef MGL_CK_PHASES
+            if (lane == 0) atomicAdd(&mgl_ck_phase_ticks[12], 1ull);
+#endif
+            if (!__builtin_amdgcn_ballot_w64(ma || mb)) break;
+        }
+        // every walk that is stuck where it stands now: the stretch to its block's left edge, where that comes before the kept
+        // row (PathWalk::edge_len) -- one more dword and 16 bases of both sequences per walk, one memory latency per block round
+        {
+            const int ea = wa.edge_len(), eb = wb.edge_len();
+            if (__builtin_amdgcn_ballot_w64((ea | eb) != 0)) {
+                unsigned ta[5], qa[5], tb[5], qb[5], ha = 0u, hb = 0u;
+                WinShift sa = {0u, 0u}, sb = {0u, 0u};
+                if (ea) {
+                    sa = wa.win_load(wm, 0, tblocks, qblocks, geom, ta, qa);
+                    ha = wa.edge_load(wm, nb, ea);
+                }
+                if (eb) {
+                    sb = wb.win_load(wm, 1, tblocks, qblocks, geom, tb, qb);
+                    hb = wb.edge_load(wm, nb, eb);
+                }
+                const bool xa = wa.edge_apply(ha, ta, qa, sa, ea, 0, geom), xb = wb.edge_apply(hb, tb, qb, sb, eb, 1, geom);
+#ifdef MGL_CK_PHASES
+                const unsigned long long took_ = __popcll(__builtin_amdgcn_ballot_w64(xa)) + __popcll(__builtin_amdgcn_ballot_w64(xb));
+                const unsigned long long tried_ = __popcll(__builtin_amdgcn_ballot_w64(ea != 0)) + __popcll(__builtin_amdgcn_ballot_w64(eb != 0));
+                if (lane == 0) {
+                    atomicAdd(&mgl_ck_phase_ticks[10], took_);
+                    atomicAdd(&mgl_ck_phase_ticks[11], tried_ - took_);
+                }
+#else
+                (void)xa;
+                (void)xb;
+#endif
+            }
+        }
+    };
+    auto block_walk = [&](auto direct_form, const int kA, const int bA, const int kB, const int bB) __attribute__((always_inline)) {
+        BlockGeom geom = geom_launch;
+        geom.direct = decltype(direct_form)::value;
+        geom.codes = !decltype(direct_form)::value && codes;
+        for (;;) {
+            const bool la = wa.can_load(kA, bA), lb = wb.can_load(kB, bB);
+            // (a lane with nothing to fetch still runs apply(): a run that ends at the matrix's edge needs no flags)
+            unsigned fa[PathWalk::LOOK], fb[PathWalk::LOOK], ta[5], qa[5], tb[5], qb[5];
+            WinShift sa = {0u, 0u}, sb = {0u, 0u};
+            if (la) {
+                wa.load(wm, fa);
+                if (wa.mode == 0) sa = wa.win_load(wm, 0, tblocks, qblocks, geom, ta, qa);
+            }
+            if (lb) {
+                wb.load(wm, fb);
+                if (wb.mode == 0) sb = wb.win_load(wm, 1, tblocks, qblocks, geom, tb, qb);
+            }
+            const bool ga = wa.apply(fa, ta, qa, sa, 0, kA, bA, geom), gb = wb.apply(fb, tb, qb, sb, 1, kB, bB, geom);
+            if (!__builtin_amdgcn_ballot_w64(ga || gb)) break;
+        }
+    };
     while (!(MGL_CK_ABLATE & 1) && __builtin_amdgcn_ballot_w64(!wa.done || !wb.done) != 0) {
         if (by_score) {
-            for (;;) { // every walk standing at a cell takes the diagonal stretches whose scores add up (PathWalk::verify_apply)
-                unsigned ta[17], qa[17], tb[17], qb[17], ga[PathWalk::VB], gb[PathWalk::VB];
-                if (wa.can_verify()) {
-                    wa.win64_load(wm, 0, tblocks, qblocks, ta, qa);
-                    wa.grid_load(wm, ql, ga);
-                }
-                if (wb.can_verify()) {
-                    wb.win64_load(wm, 1, tblocks, qblocks, tb, qb);
-                    wb.grid_load(wm, ql, gb);
-                }
-                const bool ma = wa.verify_apply(ta, qa, ga, 0, geom), mb = wb.verify_apply(tb, qb, gb, 1, geom);
-#ifdef MGL_CK_PHASES
-                if (lane == 0) atomicAdd(&mgl_ck_phase_ticks[12], 1ull);
-#endif
-                if (!__builtin_amdgcn_ballot_w64(ma || mb)) break;
-            }
-            // every walk that is stuck where it stands now: the stretch to its block's left edge, where that comes before the kept
-            // row (PathWalk::edge_len) -- one more dword and 16 bases of both sequences per walk, one memory latency per block round
-            {
-                const int ea = wa.edge_len(), eb = wb.edge_len();
-                if (__builtin_amdgcn_ballot_w64((ea | eb) != 0)) {
-                    unsigned ta[5], qa[5], tb[5], qb[5], ha = 0u, hb = 0u;
-                    if (ea) {
-                        wa.win_load(wm, 0, tblocks, qblocks, ta, qa);
-                        ha = wa.edge_load(wm, nb, ea);
-                    }
-                    if (eb) {
-                        wb.win_load(wm, 1, tblocks, qblocks, tb, qb);
-                        hb = wb.edge_load(wm, nb, eb);
-                    }
-                    const bool xa = wa.edge_apply(ha, ta, qa, ea, 0, geom), xb = wb.edge_apply(hb, tb, qb, eb, 1, geom);
-#ifdef MGL_CK_PHASES
-                    const unsigned long long took_ = __popcll(__builtin_amdgcn_ballot_w64(xa)) + __popcll(__builtin_amdgcn_ballot_w64(xb));
-                    const unsigned long long tried_ = __popcll(__builtin_amdgcn_ballot_w64(ea != 0)) + __popcll(__builtin_amdgcn_ballot_w64(eb != 0));
-                    if (lane == 0) {
-                        atomicAdd(&mgl_ck_phase_ticks[10], took_);
-                        atomicAdd(&mgl_ck_phase_ticks[11], tried_ - took_);
-                    }
-#else
-                    (void)xa;
-                    (void)xb;
-#endif
-                }
-            }
+            if (direct)
+                stretches(std::true_type{});
+            else
+                stretches(std::false_type{});
             CK_PHASE(3); // stretches that add up
             if (__builtin_amdgcn_ballot_w64(!wa.done || !wb.done) == 0) break;
         }
@@ -1117,21 +1244,10 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
 #ifdef MGL_CK_PHASES
         if (lane == 0) atomicAdd(&mgl_ck_phase_ticks[8], 1ull);
 #endif
-        for (;;) {
-            const bool la = wa.can_load(kA, bA), lb = wb.can_load(kB, bB);
-            // (a lane with nothing to fetch still runs apply(): a run that ends at the matrix's edge needs no flags)
-            unsigned fa[PathWalk::LOOK], fb[PathWalk::LOOK], ta[5], qa[5], tb[5], qb[5];
-            if (la) {
-                wa.load(wm, fa);
-                if (wa.mode == 0) wa.win_load(wm, 0, tblocks, qblocks, ta, qa);
-            }
-            if (lb) {
-                wb.load(wm, fb);
-                if (wb.mode == 0) wb.win_load(wm, 1, tblocks, qblocks, tb, qb);
-            }
-            const bool ga = wa.apply(fa, ta, qa, 0, kA, bA, geom), gb = wb.apply(fb, tb, qb, 1, kB, bB, geom);
-            if (!__builtin_amdgcn_ballot_w64(ga || gb)) break;
-        }
+        if (direct)
+            block_walk(std::true_type{}, kA, bA, kB, bB);
+        else
+            block_walk(std::false_type{}, kA, bA, kB, bB);
         wa.stuck = wb.stuck = false; // either walk has moved on
         CK_PHASE(5); // the walk inside the block
     }
@@ -1194,7 +1310,11 @@ __device__ __forceinline__ void lane_ck_grid(const DpArgs &a, const TbArgs &walk
         // link, so only then) and sleeps in between; the copies do not depend on anything this grid does, so the wait ends -- and if the
         // word stands still for gate_timeout_ticks the wave raises gate_failed and leaves, its tiles undone (the host sees the flag).
         // (a tile's aligned loads may touch the first line of the pair behind its last one: the NEXT tile's pairs must have arrived too, so
-        // that no line of an input array enters a cache before its bytes are there)
+        // that no line of an input array enters a cache before its bytes are there.  Pass 2's walks read the caller's arrays as well
+        // (SeqBlocks: whole 16-byte blocks that hold at least one byte of the walk's own pair): the block of a pair's last byte may hold
+        // the first bytes of the pair behind it -- for the tile's last pair that is tile t + 1, which the wave has waited for --, and
+        // the block of its first byte the last bytes of the pair in front of it -- for the tile's first pair that is tile t - 1,
+        // whose pairs arrived before this tile's did: the chunks land in order.)
         if (arrived < a.first + min(a.count, (tile + 2) * 128)) {
             const int64_t need = a.first + min(a.count, (tile + 2) * 128);
             // ONE wave at a time looks at the host's word (round 5).  Packed inputs arrive eight times faster than the grid consumes them:
