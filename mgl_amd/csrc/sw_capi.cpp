@@ -1144,6 +1144,10 @@ int run_device(mgl_sw_ctx *ctx, hipStream_t stream, int64_t n, const SeqSet &tse
                 const char *const wse = getenv("MGL_SW_DEBUG_WALK_STAGED"); // (1: the checkpointed lane kernel's walks read the staged sequences for ASCII input too; read per call: the tests run both forms)
                 da.walk_staged = wse && atoi(wse) != 0 ? 1 : 0;
             }
+            {
+                const char *const cwe = getenv("MGL_SW_DEBUG_CK_WIDE"); // (1: the checkpointed lane kernel keeps its middle rows and checkpoints in the wide form whatever the parameters; read per call: the tests run both forms)
+                da.ck_wide = cwe && atoi(cwe) != 0 ? 1 : 0;
+            }
             da.lane_slots = 0;
             da.tile_ctr = nullptr;
             da.grid_fault = nullptr;

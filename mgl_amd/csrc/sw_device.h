@@ -71,6 +71,9 @@ struct DpArgs {
     int strip_passes;         // ... passes over the target: 2 * 64 * waves strips each (targets beyond 16 384 rows; 0 or 1: one)
     int strip_codes;          // ... and the LDS carve holds the query as one table dword per column (strip16_lds_bytes_codes): pairs whose targets are all ACGT run the base-code form
     int lane_slots;           // sw_dp16_lane_ck_kernel: wave slots of its persistent grid = regions at tb / scratch (lane_ck_slots)
+    int ck_wide;              // ... pass 1 keeps its middle rows and column checkpoints in the WIDE form ({H, E} / {H, gap value} as two 16-bit values each) even
+                              //     where the parameters allow the narrow one (H and a difference byte; MGL_SW_DEBUG_CK_WIDE=1: the tests compare both forms).
+                              //     (It stands where the struct had four bytes of padding: no other member moves, so no other kernel's arguments do.)
     unsigned *tile_ctr;       // ... two words {draws, waves out} used as ONE 64-bit atomic object (8-byte aligned), zero when the launch starts (needed when the
                               //     launch holds more tiles than slots): the waves draw their next tile from the low half and count themselves out in the high
                               //     half; the last wave out zeroes the word

@@ -153,6 +153,49 @@ struct WaveMem {
     {
         return at32<uint2>(rows, 8u * ((m & 1) ? mid_off + (unsigned)(((m >> 1) * ql + j - 1) * 64) + lane : (unsigned)(((m >> 1) * (ql + 1) + j) * 64) + lane));
     }
+    // ---- the NARROW records (NARROW = true below; launch_dp16_lane_ck says when).  In column<> eo = max(hn - (o-e), e) with hn >= e and
+    // fo = max(hn - (o-e), fr) with hn >= fr, so H - E of a kept row and H - (gap value) of a checkpoint lie in [0, o-e] in every cell
+    // that does not wrap: where o - e <= 255 the second value of a record is H minus ONE BYTE, and a lane keeps the H of four columns
+    // (rows) as one 16-byte vector.  Same region, same bases of bnd / mid / ck / blk; the records use less of the parts they replace:
+    //   mid   strip k still starts at entry k ql 64 of `mid` (512 ql bytes per strip).  Its columns go in groups of four, group g =
+    //         columns 4 g + 1 .. 4 g + 4, 1 536 bytes each: [lane] uint4 H of the four columns | [lane] uint2 the differences H - E, byte
+    //         2 u of the uint2 pair A's of column 4 g + 1 + u, byte 2 u + 1 pair B's.  A last group of THREE columns is written the same
+    //         way (its fourth column holds nothing anybody reads); a last group of one or two columns keeps the wide records, [column]
+    //         [lane] uint2 {H, E}, where the group starts (mid_tail_wide).  So four columns take 1 536 bytes of their 2 048, three all
+    //         of their 1 536, one or two their own 512 each: a strip never leaves its 512 ql bytes, whatever ql is (written whole,
+    //         the groups would: 3 ceil(ql / 4) <= ql fails for ql = 1, 2 and 5).
+    //   ck    checkpoint (strip, block) still starts at dword ((strip (nb - 1) + block - 1) 64) 64 of `ck` (16 KB each) and is twelve
+    //         [lane] uint4: 0 .. 7 = H of rows 4 x .. 4 x + 3, 8 .. 11 = the differences H - (gap value) of rows 8 x .. 8 x + 7, two bytes
+    //         per row (A, B): 12 KB of the 16.
+    // The carry rows (bnd) are the wide {H, E} in either form.
+    __device__ __forceinline__ static bool mid_tail_wide(int ql, int j) { return ((j - 1) >> 2) == (ql >> 2) && (ql & 3) != 3; } // (ql & 3 = 0: no such j)
+    template <bool NARROW>
+    __device__ __forceinline__ unsigned mid_byte_off(int strip, int ql, int j) const // H of column j (>= 1) in the strip's middle row
+    {
+        if (!NARROW) return 8u * (mid_off + (unsigned)((strip * ql + j - 1) * 64) + lane);
+        const int c = j - 1;
+        const unsigned group = 8u * mid_off + (unsigned)(strip * ql * 512 + (c >> 2) * 1536);
+        return group + (mid_tail_wide(ql, j) ? (unsigned)((c & 3) * 512) + 8u * lane : (unsigned)((c & 3) * 4) + 16u * lane);
+    }
+    template <bool NARROW>
+    __device__ __forceinline__ unsigned row16_h(int m, int ql, int j) const // H alone of row 16 m at column j, both pairs
+    {
+        if (!NARROW) return row16(m, ql, j).x; // (the wide kernels: the code they had before there were two forms)
+        return at32<unsigned>(rows, (m & 1) ? mid_byte_off<true>(m >> 1, ql, j) : 8u * ((unsigned)(((m >> 1) * (ql + 1) + j) * 64) + lane));
+    }
+    // {H, E} of row 16 m at column j in two dword loads whose addresses are selected, not branched on (m differs from lane to lane)
+    template <bool NARROW>
+    __device__ __forceinline__ uint2 row16_n(int m, int ql, int j) const
+    {
+        if (!NARROW) return row16(m, ql, j);
+        const int c = j - 1;
+        const bool bytes = (m & 1) != 0 && !mid_tail_wide(ql, j); // E is H minus a byte (else: the record's second dword)
+        const unsigned hoff = (m & 1) ? mid_byte_off<true>(m >> 1, ql, j) : 8u * ((unsigned)(((m >> 1) * (ql + 1) + j) * 64) + lane);
+        const unsigned soff = bytes ? 8u * mid_off + (unsigned)((m >> 1) * ql * 512 + (c >> 2) * 1536 + 1024 + ((c >> 1) & 1) * 4) + 8u * lane : hoff + 4u;
+        const unsigned hv = at32<unsigned>(rows, hoff), sv = at32<unsigned>(rows, soff);
+        const unsigned d = __builtin_amdgcn_perm(0u, sv, (c & 1) ? 0x0c030c02u : 0x0c010c00u); // ZERO-extended: a difference reaches 255
+        return make_uint2(hv, bytes ? pk_sub(hv, d) : sv);
+    }
     __device__ __forceinline__ unsigned qblock(int blk4, int half) const { return at32<unsigned>(seq, 4u * ((unsigned)((2 * blk4 + half) * 64) + lane)); }
     __device__ __forceinline__ unsigned tblock(int blk4, int half) const { return at32<unsigned>(seq, 4u * (t_off + (unsigned)((2 * blk4 + half) * 64) + lane)); }
     __device__ __forceinline__ unsigned flags(int cc, int r4) const { return at32<unsigned>(blku, 4u * ((unsigned)(cc * 256 + r4) + 4u * lane)); } // the block's flags: column cc, rows 4 r4 ..
@@ -397,12 +440,13 @@ struct PathWalk {
     // the stretch to the m-th kept row above the walk's cell (m = 0: the next one), cut where the diagonal leaves the matrix
     __device__ __forceinline__ int stretch_to(int m) const { return min(I - max((((I - 1) >> 4) - m) << 4, 0), J); }
     // H of those rows in stored form (both pairs of the lane)
+    template <bool NARROW>
     __device__ __forceinline__ void grid_load(const WaveMem &wm, int ql, unsigned (&w)[VB]) const
     {
 #pragma unroll
         for (int m = 0; m < VB; ++m) {
             const int L = stretch_to(m), ie = I - L, je = J - L;
-            w[m] = wm.row16(ie >> 4, ql, max(je, 1)).x; // (a stretch that ends on a border: some valid entry, not used)
+            w[m] = wm.row16_h<NARROW>(ie >> 4, ql, max(je, 1)); // (a stretch that ends on a border: some valid entry, not used)
         }
     }
     // returns true when all VB stretches were taken and the walk can try the next ones
@@ -463,9 +507,12 @@ struct PathWalk {
         return J > CK && lc < stretch_to(0) ? lc : 0;
     }
     // H[I - lc][CK b] in stored form, both pairs of the lane (the indexing of ck_block's ia / ib)
+    template <bool NARROW>
     __device__ __forceinline__ unsigned edge_load(const WaveMem &wm, int nb, int lc) const
     {
         const int r0 = I - lc - 1, b = (J - 1) / CK;
+        if (NARROW) // (WaveMem: the checkpoint's uint4 (r0 & 31) / 4, its dword r0 & 3)
+            return WaveMem::at32<unsigned>(wm.cku, (unsigned)(((r0 >> 5) * (nb - 1) + (b - 1)) * 16384 + ((r0 & (R - 1)) >> 2) * 1024 + (r0 & 3) * 4) + 16u * wm.lane);
         return WaveMem::at32<unsigned>(wm.cku, 4u * ((unsigned)((((r0 >> 5) * (nb - 1) + (b - 1)) * 64 + 2 * (r0 & (R - 1))) * 64) + wm.lane));
     }
     // (tw, qw, sh: win_load() of the walk's cell.)  Returns true when the stretch was taken.
@@ -567,7 +614,7 @@ enum : int {
 
 // ---- pass 1: strip k, score only, keeping the rows and the column checkpoints
 // (keyA / keyB: the last row's running keys; corner: H[tl][ql] of both halves in stored form -- the last strip only)
-template <int LAST, int CODES>
+template <int LAST, int CODES, bool NARROW>
 __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql, const int nb, const WaveMem &wm, const unsigned *qst, const unsigned *tst,
                                          const LaneConsts &c, const int gopen, const int gext, const int base, const bool indel, int &bestA,
                                          int &bestA_i, int &bestB, int &bestB_i, int &keyA, int &keyB, unsigned &corner)
@@ -595,6 +642,13 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
     const uint2 *bp = wm.bnd + ((size_t)k * (ql + 1) + 1) * 64; // column j of the row entering this strip
     uint2 *bo = wm.bnd + ((size_t)(k + 1) * (ql + 1) + 1) * 64; // ... of the row leaving it
     uint2 *mp = wm.mid + (size_t)k * ql * 64;
+    // NARROW: where the strip's groups and checkpoints go, as WAVE-UNIFORM bases (scalar registers, moved on by scalar adds) beside 32-bit
+    // lane offsets -- the two record sizes of a group as two POINTERS that include the lane were four registers and spilled in the loops
+    char *mg = reinterpret_cast<char *>(const_cast<uint2 *>(wm.rows)) + (size_t)8 * wm.mid_off + (size_t)k * ql * 512;
+    char *cg = reinterpret_cast<char *>(const_cast<unsigned *>(wm.cku)) + (size_t)k * (nb - 1) * 16384;
+    const unsigned l16 = 16u * wm.lane, l8 = 8u * wm.lane;
+    unsigned mh[4] = {0u, 0u, 0u, 0u}, md0 = 0u, md[2] = {0u, 0u}; // NARROW: the group's four H and its difference bytes so far
+    unsigned me[2] = {0u, 0u};                                     // ... and E of its first two columns (a last group of one or two: wide records)
     unsigned *ckp = wm.ck + (size_t)k * (nb - 1) * 64 * 64;
     unsigned hd = bp[-64].x; // H[32 k][0]
     // column u (0 .. 3) of the group whose query dwords are qa / qb
@@ -607,8 +661,18 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
         else
             column<R, true, true, false>(h, f, t, __builtin_amdgcn_perm(qb, qa, 0x0c040c00u + 0x00010001u * u), hd, e, c, nullptr, &mid);
         hd = top.x;
-        if (!(MGL_CK_ABLATE & 4)) mp[0] = mid;
-        mp += 64;
+        if (NARROW) { // (stored once per group: mid_group below)
+            mh[u] = mid.x;
+            if (u < 2) me[u] = mid.y;
+            const unsigned d = pk_sub(mid.x, mid.y);
+            if (u & 1)
+                md[u >> 1] = __builtin_amdgcn_perm(d, md0, 0x06040200u); // bytes {A, B} of column u - 1, {A, B} of column u
+            else
+                md0 = d;
+        } else {
+            if (!(MGL_CK_ABLATE & 4)) mp[0] = mid;
+            mp += 64;
+        }
         if (LAST == NOT_LAST) {
             bo[0] = make_uint2(h[R - 1], e);
         } else { // H[tl][j]
@@ -628,13 +692,37 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
         }
         if (LAST != LAST_ROW_KEYS) bo += 64;
     };
-    auto save = [&]() { // the state BEFORE column j: H[.][j-1] and the horizontal-gap values entering column j
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            ckp[(size_t)(2 * r) * 64] = h[r];
-            ckp[(size_t)(2 * r + 1) * 64] = f[r];
+    auto mid_group = [&](const int cols) { // NARROW: the group's `cols` columns (3 or 4) leave in two stores
+        if (cols == 3) md[1] = __builtin_amdgcn_perm(md0, md0, 0x06040200u); // (the third column's bytes wait in md0 for a neighbour)
+        if (!(MGL_CK_ABLATE & 4)) {
+            *reinterpret_cast<uint4 *>(mg + l16) = make_uint4(mh[0], mh[1], mh[2], mh[3]);
+            *reinterpret_cast<uint2 *>(mg + 1024 + l8) = make_uint2(md[0], md[1]);
         }
-        ckp += 64 * 64;
+        mg += 1536;
+    };
+    auto save = [&]() { // the state BEFORE column j: H[.][j-1] and the horizontal-gap values entering column j
+        if (NARROW) {
+#pragma unroll
+            for (int x = 0; x < R / 4; ++x) *reinterpret_cast<uint4 *>(cg + x * 1024 + l16) = make_uint4(h[4 * x], h[4 * x + 1], h[4 * x + 2], h[4 * x + 3]);
+#pragma unroll
+            for (int x = 0; x < R / 8; ++x) {
+                unsigned d[4];
+#pragma unroll
+                for (int y = 0; y < 4; ++y) { // rows 8 x + 2 y and the next: bytes {A, B, A, B}
+                    const int r = 8 * x + 2 * y;
+                    d[y] = __builtin_amdgcn_perm(pk_sub(h[r + 1], f[r + 1]), pk_sub(h[r], f[r]), 0x06040200u);
+                }
+                *reinterpret_cast<uint4 *>(cg + (R / 4 + x) * 1024 + l16) = make_uint4(d[0], d[1], d[2], d[3]);
+            }
+            cg += 16384;
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                ckp[(size_t)(2 * r) * 64] = h[r];
+                ckp[(size_t)(2 * r + 1) * 64] = f[r];
+            }
+            ckp += 64 * 64;
+        }
     };
     // The carry row and the query are read ONE GROUP OF FOUR COLUMNS AHEAD: what a group needs was requested at the top of the
     // group before it, so its latency -- and the acknowledgements of the stores issued in between, which s_waitcnt vmcnt counts
@@ -659,12 +747,21 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
         one_column(top1, qa, qb, 1);
         one_column(top2, qa, qb, 2);
         one_column(top3, qa, qb, 3);
+        if (NARROW) mid_group(4);
     }
     if (j <= ql) { // the last one to three columns (j - 1 is a multiple of four here)
         if (j > 1 && ((j - 1) & (CK - 1)) == 0) save();
         one_column(n0, nqa, nqb, 0);
         if (j + 1 <= ql) one_column(n1, nqa, nqb, 1);
         if (j + 2 <= ql) one_column(n2, nqa, nqb, 2);
+        if (NARROW) { // (WaveMem: a last group of three as every group, of one or two as wide records)
+            if (j + 2 <= ql) {
+                mid_group(3);
+            } else if (!(MGL_CK_ABLATE & 4)) {
+                *reinterpret_cast<uint2 *>(mg + l8) = make_uint2(mh[0], me[0]);
+                if (j + 1 <= ql) *reinterpret_cast<uint2 *>(mg + 512 + l8) = make_uint2(mh[1], me[1]);
+            }
+        }
     }
     if (LAST != NOT_LAST) { // H[tl][ql], where the walks of the non-softclip strategies start
         corner = h[R - 1];
@@ -695,7 +792,7 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
 // ---- pass 2: recompute the flags of block (sA, bA) for the low halves and of block (sB, bB) for the high halves; s = 16-row band
 // (strip s / 2, its upper or lower half), b = block of CK columns.  needA / needB: the pair's walk waits for this block (a pair
 // that does not fetches nothing; its half computes garbage nobody reads).
-template <int CODES>
+template <int CODES, bool NARROW>
 __device__ __forceinline__ void ck_block(const int sA, const int bA, const int sB, const int bB, const bool needA, const bool needB, const BlockGeom &g,
                                          const WaveMem &wm, const LaneConsts &c, const int groups = CK / 8)
 {
@@ -714,11 +811,41 @@ __device__ __forceinline__ void ck_block(const int sA, const int bA, const int s
         const unsigned ib = (unsigned)((((sB >> 1) * (g.nb - 1) + max(bB - 1, 0)) * 64 + (sB & 1) * 2 * RB) * 64) + wm.lane;
         // one half after the other (both at once: 64 registers of checkpoint values beside the 48 of the block's state -- spilled)
         unsigned v[2 * RB];
+        // NARROW: the half's 16 rows are four uint4 of H and two of difference bytes (WaveMem) -- v[] as the wide form holds it
+        auto load_narrow = [&](const int s, const int b) {
+            const unsigned off = (unsigned)(((s >> 1) * (g.nb - 1) + max(b - 1, 0)) * 16384 + (s & 1) * 4096) + 16u * wm.lane;
+            uint4 hv[RB / 4], dv[RB / 8];
+#pragma unroll
+            for (int x = 0; x < RB / 4; ++x) hv[x] = WaveMem::at32<uint4>(wm.cku, off + (unsigned)(x * 1024));
+#pragma unroll
+            for (int x = 0; x < RB / 8; ++x) dv[x] = WaveMem::at32<uint4>(wm.cku, off + (unsigned)(8192 - (s & 1) * 2048 + x * 1024));
+#pragma unroll
+            for (int x = 0; x < RB / 4; ++x) {
+                v[8 * x + 0] = hv[x].x;
+                v[8 * x + 2] = hv[x].y;
+                v[8 * x + 4] = hv[x].z;
+                v[8 * x + 6] = hv[x].w;
+            }
+#pragma unroll
+            for (int x = 0; x < RB / 8; ++x) {
+                const unsigned d[4] = {dv[x].x, dv[x].y, dv[x].z, dv[x].w};
+#pragma unroll
+                for (int y = 0; y < 4; ++y) { // rows 8 x + 2 y and the next; ZERO-extended bytes (a difference reaches 255)
+                    const int r = 8 * x + 2 * y;
+                    v[2 * r + 1] = pk_sub(v[2 * r], __builtin_amdgcn_perm(0u, d[y], 0x0c010c00u));
+                    v[2 * r + 3] = pk_sub(v[2 * r + 2], __builtin_amdgcn_perm(0u, d[y], 0x0c030c02u));
+                }
+            }
+        };
 #pragma unroll
         for (int x = 0; x < 2 * RB; ++x) v[x] = 0u;
         if (needA && bA > 0) {
+            if (NARROW) {
+                load_narrow(sA, bA);
+            } else {
 #pragma unroll
-            for (int x = 0; x < 2 * RB; ++x) v[x] = WaveMem::at32<unsigned>(wm.cku, 4u * (ia + (unsigned)(x * 64)));
+                for (int x = 0; x < 2 * RB; ++x) v[x] = WaveMem::at32<unsigned>(wm.cku, 4u * (ia + (unsigned)(x * 64)));
+            }
         }
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
@@ -730,8 +857,12 @@ __device__ __forceinline__ void ck_block(const int sA, const int bA, const int s
 #pragma unroll
         for (int x = 0; x < 2 * RB; ++x) v[x] = 0u;
         if (needB && bB > 0) {
+            if (NARROW) {
+                load_narrow(sB, bB);
+            } else {
 #pragma unroll
-            for (int x = 0; x < 2 * RB; ++x) v[x] = WaveMem::at32<unsigned>(wm.cku, 4u * (ib + (unsigned)(x * 64)));
+                for (int x = 0; x < 2 * RB; ++x) v[x] = WaveMem::at32<unsigned>(wm.cku, 4u * (ib + (unsigned)(x * 64)));
+            }
         }
 #pragma unroll
         for (int r = 0; r < RB; ++r) {
@@ -746,8 +877,8 @@ __device__ __forceinline__ void ck_block(const int sA, const int bA, const int s
     unsigned hd;
     {
         unsigned a0 = 0u, b0 = 0u; // H[16 s][CK b]
-        if (needA) a0 = wm.row16(sA, g.ql, CK * bA).x;
-        if (needB) b0 = wm.row16(sB, g.ql, CK * bB).x;
+        if (needA) a0 = wm.row16_h<NARROW>(sA, g.ql, CK * bA);
+        if (needB) b0 = wm.row16_h<NARROW>(sB, g.ql, CK * bB);
         if (sA & 1) { // (the middle rows start at column 1: column 0 by its formula)
             const int row = sA * RB;
             const int v = border(row, g.gopen, g.gext, g.indel) + row * g.gext + g.base;
@@ -768,11 +899,11 @@ __device__ __forceinline__ void ck_block(const int sA, const int bA, const int s
         for (int u = 0; u < 8; ++u) va[u] = vb[u] = make_uint2(0u, 0u);
         if (needA) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) va[u] = wm.row16(sA, g.ql, min(CK * bA + 8 * gg + u + 1, g.ql)); // (past ql: the last column again -- flags never read)
+            for (int u = 0; u < 8; ++u) va[u] = wm.row16_n<NARROW>(sA, g.ql, min(CK * bA + 8 * gg + u + 1, g.ql)); // (past ql: the last column again -- flags never read)
         }
         if (needB) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) vb[u] = wm.row16(sB, g.ql, min(CK * bB + 8 * gg + u + 1, g.ql));
+            for (int u = 0; u < 8; ++u) vb[u] = wm.row16_n<NARROW>(sB, g.ql, min(CK * bB + 8 * gg + u + 1, g.ql));
         }
         unsigned qa[2], qb[2];
 #pragma unroll
@@ -923,7 +1054,7 @@ __device__ __forceinline__ void lds_to_global(void *dst, const unsigned char *sr
 // none inside pass 1's loops.  Making slot and lane opaque per tile recomputes them instead and empties the scratch area by a third,
 // but the kernel ran 2.5 ms per 10 M pairs SLOWER (65.2 against 62.6: the opaque lane number hides its range from the address
 // arithmetic of every store of pass 1) -- measured, scripts/ck_regs_probe.sh, and left alone.)
-template <bool VIA_LDS, bool FOLD>
+template <bool VIA_LDS, bool FOLD, bool NARROW>
 __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbArgs &walk_in, const int64_t gw, const int64_t slot, const int lane, unsigned char *out_lds, const bool first)
 {
     const int64_t n_ls = (a.count + 1) >> 1;
@@ -1026,15 +1157,17 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
     int bestA = NEG_INF, bestA_i = -1, bestB = NEG_INF, bestB_i = -1;
     int keyA = INT32_MIN, keyB = INT32_MIN; // the last row's running best (row_pref above): every column's key is >= this
     unsigned corner = 0u;                   // H[tl][ql], stored form
-    const bool row_stored = ql > ROW_KEY_MAX_QL;
+    // (the narrow kernels hold no stored-row strip: with the group's registers its column loop reloaded a spilled pointer in every round,
+    // and launch_dp16_lane_ck sends them no query that long)
+    const bool row_stored = !NARROW && ql > ROW_KEY_MAX_QL;
 #define CK_STRIPS(CMP)                                                                                                                      \
     do {                                                                                                                                    \
         for (int k = 0; k < strips - 1; ++k)                                                                                                \
-            ck_strip<NOT_LAST, CMP>(k, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i, keyA, keyB, corner); \
+            ck_strip<NOT_LAST, CMP, NARROW>(k, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i, keyA, keyB, corner); \
         if (row_stored)                                                                                                                     \
-            ck_strip<LAST_ROW_STORED, CMP>(strips - 1, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i, keyA, keyB, corner); \
+            ck_strip<LAST_ROW_STORED, CMP, NARROW>(strips - 1, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i, keyA, keyB, corner); \
         else                                                                                                                                \
-            ck_strip<LAST_ROW_KEYS, CMP>(strips - 1, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i, keyA, keyB, corner); \
+            ck_strip<LAST_ROW_KEYS, CMP, NARROW>(strips - 1, tl, ql, nb, wm, qst, tst, c, gopen, gext, base, indel, bestA, bestA_i, bestB, bestB_i, keyA, keyB, corner); \
     } while (0)
     if (codes)
         CK_STRIPS(CM);
@@ -1156,11 +1289,11 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
             WinShift sa = {0u, 0u}, sb = {0u, 0u};
             if (wa.can_verify()) {
                 sa = wa.win64_load(wm, 0, tblocks, qblocks, geom, ta, qa);
-                wa.grid_load(wm, ql, ga);
+                wa.template grid_load<NARROW>(wm, ql, ga);
             }
             if (wb.can_verify()) {
                 sb = wb.win64_load(wm, 1, tblocks, qblocks, geom, tb, qb);
-                wb.grid_load(wm, ql, gb);
+                wb.template grid_load<NARROW>(wm, ql, gb);
             }
             const bool ma = wa.verify_apply(ta, qa, sa, ga, 0, geom), mb = wb.verify_apply(tb, qb, sb, gb, 1, geom);
 #ifdef MGL_CK_PHASES
@@ -1177,11 +1310,11 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
                 WinShift sa = {0u, 0u}, sb = {0u, 0u};
                 if (ea) {
                     sa = wa.win_load(wm, 0, tblocks, qblocks, geom, ta, qa);
-                    ha = wa.edge_load(wm, nb, ea);
+                    ha = wa.template edge_load<NARROW>(wm, nb, ea);
                 }
                 if (eb) {
                     sb = wb.win_load(wm, 1, tblocks, qblocks, geom, tb, qb);
-                    hb = wb.edge_load(wm, nb, eb);
+                    hb = wb.template edge_load<NARROW>(wm, nb, eb);
                 }
                 const bool xa = wa.edge_apply(ha, ta, qa, sa, ea, 0, geom), xb = wb.edge_apply(hb, tb, qb, sb, eb, 1, geom);
 #ifdef MGL_CK_PHASES
@@ -1236,9 +1369,9 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
         for (int m = 32; m >= 1; m >>= 1) reach = max(reach, __shfl_xor(reach, m));
         const int groups = __builtin_amdgcn_readfirstlane((reach + 7) >> 3); // (61.80 ms per 10 M pairs against 61.98 with every block in full)
         if (codes)
-            ck_block<CM>(kA, bA, kB, bB, !wa.done, !wb.done, geom, wm, c, groups);
+            ck_block<CM, NARROW>(kA, bA, kB, bB, !wa.done, !wb.done, geom, wm, c, groups);
         else
-            ck_block<CMP_BYTES>(kA, bA, kB, bB, !wa.done, !wb.done, geom, wm, c, groups);
+            ck_block<CMP_BYTES, NARROW>(kA, bA, kB, bB, !wa.done, !wb.done, geom, wm, c, groups);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the block's flags are in memory
         CK_PHASE(4); // a block's flags
 #ifdef MGL_CK_PHASES
@@ -1291,7 +1424,7 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
 // 1.25 M-pair launch moved between 8.9 and 9.6 ms either way, box by box) and are gone.
 // TWO kernels, one per way the results leave (VIA_LDS: in whole lines out of LDS, TbArgs::coalesced_out; else lane by lane through the
 // caller's pointers): one kernel holding both tile functions had the registers of both to colour at once (192 spilled against 66).
-template <bool VIA_LDS, bool FOLD>
+template <bool VIA_LDS, bool FOLD, bool NARROW>
 __device__ __forceinline__ void lane_ck_grid(const DpArgs &a, const TbArgs &walk, unsigned char *out_lds)
 {
     const int lane = threadIdx.x & 63;
@@ -1378,7 +1511,7 @@ __device__ __forceinline__ void lane_ck_grid(const DpArgs &a, const TbArgs &walk
 #ifdef MGL_CK_TRACE
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
 #endif
-        sw_dp16_lane_ck_tile<VIA_LDS, FOLD>(a, walk, tile, slot, lane, out_lds, tile == slot); // (later tiles: slots + a draw)
+        sw_dp16_lane_ck_tile<VIA_LDS, FOLD, NARROW>(a, walk, tile, slot, lane, out_lds, tile == slot); // (later tiles: slots + a draw)
 #ifdef MGL_CK_TRACE
         if (lane == 0 && tile < (1 << 17)) {
             unsigned hw;
@@ -1432,20 +1565,28 @@ __device__ __forceinline__ void lane_ck_grid(const DpArgs &a, const TbArgs &walk
 __global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_kernel(const DpArgs a, const TbArgs walk)
 {
     __shared__ __attribute__((aligned(16))) unsigned char out_lds[LANE_CK_OUT_LDS_BYTES]; // a tile's results on their way out
-    lane_ck_grid<true, false>(a, walk, out_lds);
+    lane_ck_grid<true, false, false>(a, walk, out_lds);
 }
 
 // results lane by lane through the caller's pointers (scattered destinations, strides the LDS form does not take); no LDS
-__global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_scatter_kernel(const DpArgs a, const TbArgs walk) { lane_ck_grid<false, false>(a, walk, nullptr); }
+__global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_scatter_kernel(const DpArgs a, const TbArgs walk) { lane_ck_grid<false, false, false>(a, walk, nullptr); }
 
 // ... the twins for parameters with a folded diagonal (a.fold_k != 0, sw_device.h: diag_fold): the base-code waves form the diagonal
-// in one v_pk_mad_u16 (sw_lane_cell.h, CMP_FOLD)
+// in one v_pk_mad_u16 (sw_lane_cell.h, CMP_FOLD) -- and keep pass 1's middle rows and checkpoints as the NARROW records (WaveMem;
+// launch_dp16_lane_ck sends them only launches whose o - e is a byte)
 __global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_kernel_fold(const DpArgs a, const TbArgs walk)
 {
     __shared__ __attribute__((aligned(16))) unsigned char out_lds[LANE_CK_OUT_LDS_BYTES];
-    lane_ck_grid<true, true>(a, walk, out_lds);
+    lane_ck_grid<true, true, true>(a, walk, out_lds);
 }
-__global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_scatter_kernel_fold(const DpArgs a, const TbArgs walk) { lane_ck_grid<false, true>(a, walk, nullptr); }
+__global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_scatter_kernel_fold(const DpArgs a, const TbArgs walk) { lane_ck_grid<false, true, true>(a, walk, nullptr); }
+// ... and the folded diagonal with the WIDE records, for the folding parameter sets the narrow ones do not take
+__global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_kernel_fold_wide(const DpArgs a, const TbArgs walk)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char out_lds[LANE_CK_OUT_LDS_BYTES];
+    lane_ck_grid<true, true, false>(a, walk, out_lds);
+}
+__global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_scatter_kernel_fold_wide(const DpArgs a, const TbArgs walk) { lane_ck_grid<false, true, false>(a, walk, nullptr); }
 
 // either wire format, the same for both sequence sets (the kernel stages base codes, sw_lane_cell.h)
 bool lane16_ck_supported(const SeqSet &t, const SeqSet &q) { return (t.packed2 != 0) == (q.packed2 != 0); }
@@ -1460,10 +1601,18 @@ hipError_t launch_dp16_lane_ck(const DpArgs &a, const TbArgs &walk, hipStream_t 
     const int64_t tiles = ((a.count + 1) / 2 + 63) / 64;
     if (a.lane_slots < 1 || (tiles > a.lane_slots && !a.tile_ctr)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(tiles < a.lane_slots ? tiles : a.lane_slots)), block(64);
+    // The narrow records (WaveMem) are a form of the *_fold twins: one form per kernel, chosen here, so that no store of pass 1 stands
+    // behind a run-time branch and no kernel holds the registers of both forms.  They need 0 <= o - e <= 255 and a last row that is
+    // not stored (a.uni_ql bounds the query of every wave of a grouped launch); a folding parameter set outside that, and
+    // MGL_SW_DEBUG_CK_WIDE=1, take the *_fold_wide kernels: the same arithmetic, the wide records.  Parameters without a folded
+    // diagonal keep the wide records (the narrow form of the unfolded kernels would be four kernels more for the slower half of the sets).
+    const int o_e = a.gopen - a.gext;
+    const bool narrow = !a.ck_wide && o_e >= 0 && o_e <= 255 && a.uni_ql <= ROW_KEY_MAX_QL;
     if (walk.coalesced_out)
-        hipLaunchKernelGGL(a.fold_k ? sw_dp16_lane_ck_kernel_fold : sw_dp16_lane_ck_kernel, grid, block, 0, stream, a, walk);
+        hipLaunchKernelGGL(!a.fold_k ? sw_dp16_lane_ck_kernel : narrow ? sw_dp16_lane_ck_kernel_fold : sw_dp16_lane_ck_kernel_fold_wide, grid, block, 0, stream, a, walk);
     else
-        hipLaunchKernelGGL(a.fold_k ? sw_dp16_lane_ck_scatter_kernel_fold : sw_dp16_lane_ck_scatter_kernel, grid, block, 0, stream, a, walk);
+        hipLaunchKernelGGL(!a.fold_k ? sw_dp16_lane_ck_scatter_kernel : narrow ? sw_dp16_lane_ck_scatter_kernel_fold : sw_dp16_lane_ck_scatter_kernel_fold_wide, grid, block, 0,
+                           stream, a, walk);
     return hipGetLastError();
 }
 
