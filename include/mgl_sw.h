@@ -777,8 +777,9 @@ int mgl_sw_chain_anchors_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
  * merge), sw_seed_scan_kernel (d_cand_start_out and the capacity cut) and sw_seed_pack_kernel (the candidates into their CSR place), out
  * of one borrowing of the context's workspace.  This stage has no MGL_SW_KERNEL_* id: mgl_sw_ctx_get_timing's fill_kernel stays what it
  * was (the other fields are reset as by every device entry).
- * LIMITS: forward strand only (both: mgl_sw_seed_strands_batch_device below); the pair's own window, no index; k <= 16; a query's sketch and a pair's raw hits are bounded at 8192; no
- * occurrence cap on the window's side; the batch is staged whole.
+ * LIMITS: forward strand only (both: mgl_sw_seed_strands_batch_device below); the pair's own window (against an index of a whole
+ * reference: mgl_sw_seed_index_batch_device below); k <= 16; a query's sketch and a pair's raw hits are bounded
+ * at 8192; no occurrence cap on the window's side (mgl_sw_seed_index_batch_device has one); the batch is staged whole.
  */
 int mgl_sw_seed_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets, const int64_t *d_t_start, const int32_t *d_t_len,
                              const uint8_t *d_queries, const int64_t *d_q_start, const int32_t *d_q_len, int k, int w, int max_occ, int merge,
@@ -837,6 +838,85 @@ int mgl_sw_select_strand_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
                                       const int32_t *d_chain_len, const int32_t *d_chain_score, int64_t total_chain, int64_t query_bytes,
                                       int32_t *d_strand_out, uint8_t *d_queries_out, int64_t *d_anchor_start_out, int32_t *d_anchor_t_out,
                                       int32_t *d_anchor_q_out, int32_t *d_anchor_len_out, int32_t *d_score_out, int32_t *d_status_out);
+
+/*
+ * A MINIMIZER INDEX OF ONE REFERENCE (NOT a reference function; opt-in): what the seed stages above lack -- with it a read needs no
+ * window of its own.  Defined by tests/index_textbook.py (build_index): the sketch of the reference (ref_len bytes at d_ref, device
+ * memory, ASCII) by mgl_sw_seed_batch_device's definition, as M entries (key, position) ascending by (key, position).  k in 4 .. 16, w in
+ * 1 .. 32, ref_len in 1 .. 2^31 - 1; positions are int32; M = 0 (a reference shorter than k, or without a valid k-mer) is a valid
+ * index.  A key is the whole k-mer, so a hit is an exact match without the reference being read.
+ * The handle is an opaque device object with allocations of its OWN -- not the context's workspace: it outlives calls --; several may
+ * live on one context; it does not keep d_ref.  mgl_sw_index_build_device SYNCHRONISES `stream` -- it learns M before it allocates M
+ * entries --, the one entry of this family that does.  *out is null on every failure.  mgl_sw_index_destroy(NULL) is harmless; an index
+ * is destroyed before its device is reset, in any order with its context.
+ * mgl_sw_index_get_info: ref_len, k, w, entries = M, bytes = the index's device memory (8 per entry and the bucket table).
+ * mgl_sw_index_export_device: the M entries ascending into d_keys_out and d_pos_out (device memory, `capacity` entries each), enqueued
+ * on `stream`, not synchronised; the internal layout is not part of the interface.
+ * MGL_SW_ERR_BAD_ARG before any device work for a null pointer (a null index included), ref_len, k or w outside its range, capacity
+ * below M; MGL_SW_ERR_DEVICE without a GPU; a failed allocation is MGL_SW_ERR_NOMEM or MGL_SW_ERR_DEVICE as the runtime reports it.
+ * Device work of the build: sw_index_sketch_kernel twice (a count per block of 1024 positions, then the entries), sw_index_scan_kernel
+ * between them, rocPRIM's radix sort over bits [0, 32 + 2k), sw_index_split_kernel, sw_index_bucket_kernel (a table over the top
+ * min(2k, 24, max(10, ceil(log2 M))) bits of a key).  Scratch of the build -- 16 bytes per entry and the sort's -- is freed before it
+ * returns.  No MGL_SW_KERNEL_* id.
+ * LIMITS: ONE reference sequence (contigs concatenated by the caller need at least k non-ACGT bytes between them, and a chain may
+ * still span a boundary); ref_len < 2^31; k <= 16; the build synchronises.
+ */
+typedef struct mgl_sw_index mgl_sw_index;
+typedef struct mgl_sw_index_info {
+    int64_t ref_len, entries, bytes;
+    int32_t k, w;
+} mgl_sw_index_info;
+int mgl_sw_index_build_device(mgl_sw_ctx *ctx, void *stream, const uint8_t *d_ref, int64_t ref_len, int k, int w, mgl_sw_index **out);
+void mgl_sw_index_destroy(mgl_sw_index *idx);
+int mgl_sw_index_get_info(const mgl_sw_index *idx, mgl_sw_index_info *out);
+int mgl_sw_index_export_device(const mgl_sw_index *idx, void *stream, uint32_t *d_keys_out, int32_t *d_pos_out, int64_t capacity);
+
+/*
+ * SEEDING AGAINST THE INDEX (NOT a reference function; opt-in): mgl_sw_seed_strands_batch_device with the whole reference for every
+ * read's window.  Defined by tests/index_textbook.py (seed_index_row, seed_index_batch).  strands = 1: n rows, row p = Q_p; strands = 2:
+ * 2n rows, row 2p = Q_p and row 2p + 1 = rc(Q_p).  Per row, with occ_Q(x) the positions of the row's sketch with key x and occ_I(x) the
+ * index's entries with key x: every position q of the sketch with 1 <= occ_Q(x) <= max_occ and 1 <= occ_I(x) <= max_occ_ref gives one
+ * raw hit (t, q, k) per entry t; R_p is their number after both caps; merge, order, statuses (ql < 1; a sketch above 8192 positions or
+ * R_p > max_cand; the capacity rule in row order) and the output layouts are mgl_sw_seed_strands_batch_device's over strands * n rows,
+ * with d_row_t_len_out = ref_len for every row.  Where no key of the index occurs more than max_occ_ref times a row is what
+ * mgl_sw_seed_batch_device gives for (the reference, the oriented read).  k and w are the index's.  max_occ_ref in 1 .. 8192: the cap
+ * on the window's side that mgl_sw_seed_batch_device lacks.  Optional outputs: d_row_t_len_out, d_row_q_len_out, d_status_out.
+ * With total_cand = cand_capacity the outputs are valid arguments of mgl_sw_chain_anchors_batch_device as they are.
+ * MGL_SW_ERR_BAD_ARG before any device work for a null required pointer, strands not 1 or 2, n outside [0, 2^30 / strands], max_occ,
+ * max_occ_ref, merge, max_cand or cand_capacity outside its range; MGL_SW_ERR_DEVICE without a GPU; MGL_SW_ERR_NOMEM where the
+ * workspace limit does not hold the rows' staging (4 + 12 max_cand bytes per row) beside one slot (64 KiB, 160 KiB where max_cand is
+ * above 2048).
+ * Device work, all on `stream`, no synchronisation: sw_seed_index_kernel (one workgroup per read, persistent: a row's sketch sorted by
+ * key, one lookup per distinct key through the bucket table, the merge), sw_seed_scan_kernel, sw_seed_pack_kernel.  No MGL_SW_KERNEL_*
+ * id: mgl_sw_ctx_get_timing's fill_kernel stays what it was.
+ * LIMITS: one chain per read follows from this stage: no secondary hits, no mapping quality; a read's raw hits over the WHOLE reference
+ * are bounded by max_cand.
+ */
+int mgl_sw_seed_index_batch_device(mgl_sw_ctx *ctx, void *stream, const mgl_sw_index *idx, int64_t n, const uint8_t *d_queries,
+                                   const int64_t *d_q_start, const int32_t *d_q_len, int strands, int max_occ, int max_occ_ref, int merge,
+                                   int max_cand, int64_t cand_capacity, int64_t *d_cand_start_out, int32_t *d_cand_t_out, int32_t *d_cand_q_out,
+                                   int32_t *d_cand_len_out, int32_t *d_row_t_len_out, int32_t *d_row_q_len_out, int32_t *d_status_out);
+
+/*
+ * THE WINDOW OF A CHAIN (NOT a reference function; opt-in): between the chain stage (or mgl_sw_select_strand_batch_device) over rows
+ * seeded against an index and mgl_sw_align_chain_batch_device.  Defined by tests/index_textbook.py (locate_window).  Per pair with
+ * K >= 1 anchors (d_anchor_start, int64, n + 1; the anchors' t in the reference's coordinates), first (t0, q0, l0) and last
+ * (tK, qK, lK), ql = d_q_len[p], in 64 bits: lo = max(0, t0 - q0 - slack), hi = min(ref_len, tK + lK + (ql - qK - lK) + slack);
+ * d_t_start_out[p] = lo, d_t_len_out[p] = hi - lo, and every anchor's t - lo goes to d_anchor_t_out, which may be d_anchor_t itself.
+ * K = 0: t_start = 0, t_len = 0, status 0 -- the read is unmapped, and the alignment refuses it as it refuses a pair without anchors.
+ * d_status_out (optional): MGL_SW_ERR_BAD_ARG for ql < 1, a range of d_anchor_start that descends or leaves [0, total_anchors], or an
+ * anchor with l < 1, t < 0, q < 0, t + l > ref_len or q + l > ql; MGL_SW_ERR_UNSUPPORTED for hi - lo > max_tl.  A refused pair has
+ * t_start = 0, t_len = 0 and none of its anchors written.
+ * Then d_ref, d_t_start_out, d_t_len_out and the rebased anchors are valid arguments of mgl_sw_align_chain_batch_device as they are:
+ * the window is never copied.
+ * MGL_SW_ERR_BAD_ARG before any device work for a null required pointer, n or total_anchors outside [0, 2^30], ref_len outside
+ * 1 .. 2^31 - 1, slack < 0 or max_tl < 1; MGL_SW_ERR_DEVICE without a GPU.
+ * Device work on `stream`, no synchronisation, no workspace: sw_locate_window_kernel (a wave per pair).  No MGL_SW_KERNEL_* id.
+ */
+int mgl_sw_locate_window_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, int64_t ref_len, const int32_t *d_q_len,
+                                      const int64_t *d_anchor_start, const int32_t *d_anchor_t, const int32_t *d_anchor_q,
+                                      const int32_t *d_anchor_len, int64_t total_anchors, int slack, int max_tl, int64_t *d_t_start_out,
+                                      int32_t *d_t_len_out, int32_t *d_anchor_t_out, int32_t *d_status_out);
 
 /*
  * Logical backtrack matrix of one pair, the reference's calculateMatrix

@@ -35,7 +35,8 @@ SYMBOLS = (
     "mgl_sw_explain_sized", "mgl_sw_ctx_check", "mgl_sw_local_batch_device_matrix", "mgl_sw_align_batch_device_banded",
     "mgl_sw_extend_batch_device", "mgl_sw_extend_seed_batch_device", "mgl_sw_align_chain_batch_device",
     "mgl_sw_chain_anchors_batch_device", "mgl_sw_seed_batch_device", "mgl_sw_seed_strands_batch_device",
-    "mgl_sw_select_strand_batch_device",
+    "mgl_sw_select_strand_batch_device", "mgl_sw_index_build_device", "mgl_sw_index_destroy", "mgl_sw_index_get_info",
+    "mgl_sw_index_export_device", "mgl_sw_seed_index_batch_device", "mgl_sw_locate_window_batch_device",
 )
 # MGL_SW_VERSION of the include/mgl_sw.h this mirror was written against: the structs below (Plan, Timing) are that header's, and the
 # library writes sizeof(ITS struct) through the pointers it is given -- so a library of another version is refused at load time
@@ -65,6 +66,11 @@ class SeedAlignment(C.Structure):
 class ChainAlignment(C.Structure):
     """mgl_sw_chain_alignment: one pair's chain alignment (mgl_sw_align_chain_batch_device)."""
     _fields_ = [(n, C.c_int32) for n in ("score", "t_beg", "t_end", "q_beg", "q_end", "anchor_score", "dropped", "cigar_from")]
+
+
+class IndexInfo(C.Structure):
+    """mgl_sw_index_info: what mgl_sw_index_get_info says about a minimizer index."""
+    _fields_ = [(n, C.c_int64) for n in ("ref_len", "entries", "bytes")] + [(n, C.c_int32) for n in ("k", "w")]
 
 
 class Timing(C.Structure):
@@ -188,6 +194,13 @@ def lib():
     L.mgl_sw_seed_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp] + [C.c_int] * 5 + [C.c_int64] + [vp] * 5
     L.mgl_sw_seed_strands_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp] + [C.c_int] * 5 + [C.c_int64] + [vp] * 7
     L.mgl_sw_select_strand_batch_device.argtypes = [vp, vp, C.c_int64] + [vp] * 8 + [C.c_int64] * 2 + [vp] * 8
+    L.mgl_sw_index_build_device.argtypes = [vp, vp, vp, C.c_int64, C.c_int, C.c_int, C.POINTER(vp)]
+    L.mgl_sw_index_destroy.argtypes = [vp]
+    L.mgl_sw_index_destroy.restype = None
+    L.mgl_sw_index_get_info.argtypes = [vp, C.POINTER(IndexInfo)]
+    L.mgl_sw_index_export_device.argtypes = [vp, vp, vp, vp, C.c_int64]
+    L.mgl_sw_seed_index_batch_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp] + [C.c_int] * 5 + [C.c_int64] + [vp] * 7
+    L.mgl_sw_locate_window_batch_device.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int] + [vp] * 4
     L.mgl_sw_backtrack_matrix.argtypes = [cp, C.c_int, cp, C.c_int] + [C.c_int] * 5 + [i32p, C.POINTER(Score)]
     L.mgl_sw_cigar_from_backtrack.argtypes = [i32p, C.c_int, C.c_int, C.c_int, C.POINTER(Score), cp, C.c_int,
                                               C.POINTER(C.c_int), C.POINTER(C.c_int)]

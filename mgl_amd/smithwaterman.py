@@ -40,6 +40,50 @@ SeedExtendResult = namedtuple("SeedExtendResult", "score t_beg t_end q_beg q_end
 ChainAlignResult = namedtuple("ChainAlignResult", "score t_beg t_end q_beg q_end anchor_score dropped cigar_from cigars cigar_len")
 ChainAnchorsResult = namedtuple("ChainAnchorsResult", "chains score status")
 SeedResult = namedtuple("SeedResult", "candidates status")
+MapResult = namedtuple("MapResult", "ref_beg ref_end strand score cigars status")
+IndexInfo = namedtuple("IndexInfo", "ref_len entries bytes k w")
+
+
+class Index:
+    """A minimizer index of one reference on the device (mgl_sw_index, include/mgl_sw.h; ``MicrosoftSmithWaterman.build_index``
+    makes it).  It owns the native handle and keeps ``ref``, the reference's device tensor, which the index itself does not."""
+
+    def __init__(self, handle, ref):
+        self.handle, self.ref = handle, ref
+
+    @property
+    def info(self):
+        out = _lib.IndexInfo()
+        _check(_lib.lib().mgl_sw_index_get_info(self.handle, C.byref(out)))
+        return IndexInfo(out.ref_len, out.entries, out.bytes, out.k, out.w)
+
+    def export(self):
+        """-> (keys uint32 [M], positions int32 [M]) tensors, ascending by (key, position); enqueued on the current stream"""
+        import torch
+
+        m = self.info.entries
+        keys, pos = torch.empty(m, dtype=torch.int32, device=self.ref.device), torch.empty(m, dtype=torch.int32, device=self.ref.device)
+        spare = torch.empty(2, dtype=torch.int64, device=self.ref.device)  # an empty tensor has no address: the entry wants one
+        _check(_lib.lib().mgl_sw_index_export_device(self.handle, torch.cuda.current_stream(self.ref.device).cuda_stream, keys.data_ptr() or spare.data_ptr(),
+                                                     pos.data_ptr() or spare.data_ptr(), m))
+        return keys.view(torch.uint32), pos
+
+    def close(self):
+        if self.handle is not None:
+            _lib.lib().mgl_sw_index_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class CigarColumn:
@@ -611,6 +655,141 @@ class MicrosoftSmithWaterman:
         aln = self.align_chain_device(targets, t_start, t_len, chosen[1], q_start, q_len, *chosen[2:6], max_tl, max_ql, dist_t, dist_q, band, zdrop,
                                       parameters, **align)
         return seeds, chain, chosen, aln
+
+    def build_index(self, ref, k=15, w=10):
+        """mgl_sw_index_build_device: the minimizer index of one reference, built on the device (tests/index_textbook.py).  ``ref``:
+        a uint8 tensor on this context's GPU, or bytes (copied there).  NOT a reference function.  Synchronises the current stream.
+        Returns an ``Index``, which keeps the reference tensor: ``map_reads_device`` aligns against it in place.  No byte beyond the
+        reference is read by any stage (the band kernels load a window's bytes one by one), so the tensor needs no padding."""
+        import torch
+
+        ctx = self._ensure()
+        dev = torch.device("cuda", self._device)
+        if not isinstance(ref, torch.Tensor):
+            ref = torch.from_numpy(np.frombuffer(bytes(ref), dtype=np.uint8).copy()).to(dev)
+        assert ref.dtype == torch.uint8 and ref.is_contiguous()
+        handle = C.c_void_p()
+        rc = _lib.lib().mgl_sw_index_build_device(ctx, torch.cuda.current_stream(dev).cuda_stream, ref.data_ptr() or None, int(ref.numel()), int(k), int(w),
+                                                  C.byref(handle))
+        _check(rc, ctx)
+        return Index(handle, ref)
+
+    def seed_index(self, index, queries, strands=2, max_occ=8, max_occ_ref=64, merge=True, max_cand=4096):
+        """mgl_sw_seed_index_batch_device over a list of byte strings: ``seed_strands`` with the whole indexed reference for every
+        read's window -- no window is needed (tests/index_textbook.py).  A key that occurs more than ``max_occ`` times in a read's
+        sketch or more than ``max_occ_ref`` times in the index is dropped.  NOT a reference function.  Returns SeedResult over the
+        ``strands`` * n rows; a candidate's t is a position of the reference."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        qs = [bytes(q) for q in queries]
+        n, packed, _ = _pack_pairs(qs, qs, dev, 16, False)
+        out = self.seed_index_device(index, *packed[3:6], strands, max_occ, max_occ_ref, merge, max_cand)
+        torch.cuda.synchronize(dev)
+        cs, ct, cq, cl, _, _, st = (x.cpu().numpy() for x in out)
+        return SeedResult([[(int(ct[i]), int(cq[i]), int(cl[i])) for i in range(cs[r], cs[r + 1])] for r in range(strands * n)], st)
+
+    def seed_index_device(self, index, queries, q_start, q_len, strands=2, max_occ=8, max_occ_ref=64, merge=True, max_cand=4096, cand_capacity=None,
+                          out=None):
+        """The device-tensor form: ``seed_strands_device``'s read arguments and its tuple over the ``strands`` * n rows (row_t_len is
+        the reference's length); enqueued on the current stream, not synchronised.  ``cand_capacity`` defaults to strands * n *
+        max_cand, which always fits."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(q_start.numel())
+        rows = max(int(strands), 0) * n
+        dev = queries.device
+        if cand_capacity is None:
+            cand_capacity = int(out[1].numel()) if out is not None else min(rows * int(max_cand), 1 << 30)
+        if out is None:
+            i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
+            out = (torch.empty(rows + 1, dtype=torch.int64, device=dev), i32(cand_capacity), i32(cand_capacity), i32(cand_capacity), i32(rows), i32(rows),
+                   i32(rows))
+        cs, ct, cq, cl, rt, rq, st = out
+        assert min(ct.numel(), cq.numel(), cl.numel()) >= cand_capacity and cs.numel() >= rows + 1
+        assert all(x is None or x.numel() >= rows for x in (rt, rq, st))
+        spare = torch.empty(2, dtype=torch.int64, device=dev) if n == 0 or cand_capacity == 0 else None  # an empty tensor has no address: the entry wants one
+        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        rc = _lib.lib().mgl_sw_seed_index_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, index.handle, n, ptr(queries), ptr(q_start), ptr(q_len), int(strands), int(max_occ),
+            int(max_occ_ref), int(merge), int(max_cand), int(cand_capacity), ptr(cs), ptr(ct), ptr(cq), ptr(cl), ptr(rt), ptr(rq), ptr(st))
+        _check(rc, ctx)
+        return out
+
+    def locate_window_device(self, index_or_ref_len, q_len, anchor_start, anchor_t, anchor_q, anchor_len, slack, max_tl, out=None, in_place=False):
+        """mgl_sw_locate_window_batch_device on device tensors: every read's chain (``chain_anchors_device``'s or
+        ``select_strand_device``'s anchor arrays, t in the reference's coordinates) -> its window of the reference, ``slack`` bases
+        beyond what the read's ends need, and the anchors' t relative to it (tests/index_textbook.py); enqueued on the current
+        stream, not synchronised.  Returns (t_start [n] int64, t_len [n] int32, anchor_t [as anchor_t] int32, status [n]) tensors;
+        ``out``: such a tuple to write into (its status may be None); ``in_place``: the rebased t overwrite ``anchor_t``.  With the
+        reference for the targets they are ``align_chain_device``'s arguments as they are.  A read without anchors has t_len 0."""
+        import torch
+
+        ctx = self._ensure()
+        ref_len = index_or_ref_len.info.ref_len if isinstance(index_or_ref_len, Index) else int(index_or_ref_len)
+        n = int(q_len.numel())
+        total = int(anchor_t.numel())
+        dev = q_len.device
+        if out is None:
+            out = (torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                   anchor_t if in_place else torch.empty(total, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+        ts, tl, at, st = out
+        assert anchor_start.numel() >= n + 1 and min(anchor_q.numel(), anchor_len.numel(), at.numel()) >= total and min(ts.numel(), tl.numel()) >= n
+        spare = torch.empty(2, dtype=torch.int64, device=dev)  # an empty tensor has no address: the entry wants one
+        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        rc = _lib.lib().mgl_sw_locate_window_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ref_len, ptr(q_len), ptr(anchor_start), ptr(anchor_t), ptr(anchor_q), ptr(anchor_len), total,
+            int(slack), int(max_tl), ptr(ts), ptr(tl), ptr(at), ptr(st))
+        _check(rc, ctx)
+        return out
+
+    def map_reads_device(self, index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters=GATK_PARAMETERS, slack=200, strands=2, max_occ=8,
+                         max_occ_ref=64, merge=True, max_cand=4096, cand_capacity=None, seed_out=None, max_pred=64, max_dist=5000, bw=500, pen_gap=38,
+                         pen_skip=0, chain_out=None, select_out=None, locate_out=None, **align):
+        """Reads in, positions and CIGARs out, on the current stream: ``seed_index_device`` -> ``chain_anchors_device`` over the rows
+        -> (``strands`` = 2) ``select_strand_device`` -> ``locate_window_device`` -> ``align_chain_device`` on the index's reference
+        in place, nothing read back and nothing synchronised in between.  ``max_tl`` bounds a read's window of the reference;
+        ``align``: the further arguments of ``align_chain_device``.  Returns (the seed stage's tuple, the chain stage's tuple, the
+        choice's tuple or None, the window's tuple, the alignment's tuple).  The alignment's t_beg / t_end are relative to the read's
+        window: on the reference it spans [t_start + t_beg, t_start + t_end); q and the CIGAR are the ORIENTED read's, as in
+        ``align_reads_strands_device``.  A read without a chain (unmapped) has t_len 0 and is status MGL_SW_ERR_BAD_ARG in the
+        alignment's tuple."""
+        seeds = self.seed_index_device(index, queries, q_start, q_len, strands, max_occ, max_occ_ref, merge, max_cand, cand_capacity, out=seed_out)
+        chain = self.chain_anchors_device(seeds[4], seeds[5], *seeds[:4], max_cand, max_pred, max_dist, bw, pen_gap, pen_skip, out=chain_out)
+        chosen = self.select_strand_device(queries, q_start, q_len, *chain[:5], out=select_out) if strands == 2 else None
+        oriented, anchors = (chosen[1], chosen[2:6]) if chosen is not None else (queries, chain[:4])
+        window = self.locate_window_device(index, q_len, *anchors, slack, max_tl, out=locate_out)
+        dist_t, dist_q = (max_dist, max_dist) if np.isscalar(max_dist) else max_dist
+        aln = self.align_chain_device(index.ref, window[0], window[1], oriented, q_start, q_len, anchors[0], window[2], anchors[2], anchors[3], max_tl,
+                                      max_ql, dist_t, dist_q, band, zdrop, parameters, **align)
+        return seeds, chain, chosen, window, aln
+
+    def map_reads(self, index, reads, band=64, zdrop=-1, parameters=GATK_PARAMETERS, slack=200, strands=2, max_tl=None, **stages):
+        """``map_reads_device`` over a list of byte strings.  ``max_tl`` defaults to 1.5 times the longest read and the slack to
+        either side; ``stages``: the further arguments of ``map_reads_device``.  Returns MapResult, per read: ``ref_beg`` and
+        ``ref_end`` (the alignment spans [ref_beg, ref_end) of the reference), ``strand``, ``score``, ``cigars`` (of the oriented
+        read) and ``status`` (0; the window's status where it refused the read; MGL_SW_ERR_BAD_ARG for an unmapped read -- such a
+        read's other fields are 0 and its CIGAR empty; no exception for a read's status)."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        qs = [bytes(q) for q in reads]
+        n, packed, _ = _pack_pairs(qs, qs, dev, 16, False)
+        max_ql = packed[7]
+        if max_tl is None:
+            max_tl = max_ql + max_ql // 2 + 2 * int(slack)
+        stride = stages.pop("cigar_stride", None) or _default_stride(max_tl, max_ql, False)
+        _, _, chosen, window, aln = self.map_reads_device(index, *packed[3:6], max_tl, max_ql, band, zdrop, parameters, slack, strands, cigar_stride=stride,
+                                                          **stages)
+        torch.cuda.synchronize(dev)
+        rec, cg, ln, st = aln[0].cpu().numpy(), aln[4].cpu().numpy().reshape(n, stride), aln[5].cpu().numpy(), aln[6].cpu().numpy()
+        t_start, wst = window[0].cpu().numpy(), window[3].cpu().numpy()
+        ok = st == 0
+        strand = chosen[0].cpu().numpy() if chosen is not None else np.zeros(n, np.int32)
+        ln = np.where(ok, ln, 0).astype(np.int32)
+        return MapResult(np.where(ok, t_start + rec[:, 1], 0), np.where(ok, t_start + rec[:, 2], 0), np.where(ok, strand, 0).astype(np.int32),
+                         np.where(ok, rec[:, 0], 0).astype(np.int32), CigarColumn(cg, ln), np.where(wst != 0, wst, st).astype(np.int32))
 
     def align_packed_2bit(self, target_bases, target_base_count, t_start, t_len, query_bases, query_base_count, q_start, q_len,
                           max_tl, max_ql, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,

@@ -175,3 +175,21 @@ def noisy_candidates(rng, tl, ql, chain, decoys=2.0, repeats=0.5, overlaps=0.5, 
                     out.append((nt, nq, l, kind))
     out.sort()
     return [c[:3] for c in out], [c[3] for c in out]
+
+
+def mapping_set(seed, count, length=10000, spacer=3000):
+    """Reads with a known place on one reference: the windows of ``chain_pairs(seed, count, length)`` laid into one random reference
+    with ``spacer`` random bases in front of, between and behind them; every odd read is given reverse-complemented.
+    -> (ref, reads, truth), truth[p] = (the position of T_p in ref, len(T_p), the strand of read p)."""
+    pairs = chain_pairs(seed, count, length)
+    rng = np.random.default_rng([seed, count, length, spacer])
+    parts, truth, at = [], [], 0
+    for p, (T, _, _) in enumerate(pairs):
+        parts.append(BASES[rng.integers(4, size=spacer)].tobytes())
+        at += spacer
+        truth.append((at, len(T), p % 2))
+        parts.append(T)
+        at += len(T)
+    parts.append(BASES[rng.integers(4, size=spacer)].tobytes())
+    reads = [revcomp(Q) if p % 2 else Q for p, (_, Q, _) in enumerate(pairs)]
+    return b"".join(parts), reads, truth
