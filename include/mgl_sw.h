@@ -919,6 +919,47 @@ int mgl_sw_locate_window_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
                                       int32_t *d_t_len_out, int32_t *d_anchor_t_out, int32_t *d_status_out);
 
 /*
+ * SECONDARY CHAINS AND MAPPING QUALITY (NOT a reference function; opt-in): behind mgl_sw_chain_anchors_batch_device, beside the strand
+ * choice.  Defined by tests/rank_textbook.py; DESIGN.md section 9k.  The n reads have `strands` rows each (1 or 2: rows strands * p ..,
+ * as mgl_sw_seed_index_batch_device lays them out); row r has the candidates d_cand_start[r] .. d_cand_start[r + 1] (int64, n * strands
+ * + 1), d_row_q_len[r], the chain stage's d_f / d_pred for them (its optional outputs d_f_out / d_pred_out; pred relative to the row's
+ * first candidate, -1: none) and, optionally, its status d_row_status[r].
+ * Per row the candidates are visited by (f descending, index ascending); an unused one with f >= min_score starts a walk along pred
+ * that marks what it passes and stops at -1 or at a used candidate i; the chain scores f(end) or f(end) - f(i) and is kept iff its
+ * score >= min_score and its anchors K >= min_cnt.  The kept chains of a read's rows are ranked by (score descending, strand ascending,
+ * end_index ascending) and cut to max_chains (1 .. 16).  In rank order a chain whose interval on the forward read overlaps an earlier
+ * primary chain's by mask_level / 256 (1 .. 256; minimap2's 0.5 is 128) of the shorter of the two is that chain's secondary; otherwise
+ * it is primary (parent = its own rank).  A primary chain gets mapq 0 .. 60 from its score, its best secondary's score (subsc), their
+ * number (n_sub) and K, in integers; a secondary chain has mapq, n_sub and subsc 0.  No parity with minimap2 is claimed.
+ * d_n_chains_out[p]: the chains of read p; d_records_out[p * max_chains ..]: their records in rank order -- records at or beyond
+ * n_chains are not written.  t_beg / t_end / q_beg / q_end are the row's own oriented coordinates; end_index is the chain's last
+ * candidate, from the row's first.  The first record of a read is the chain mgl_sw_select_strand_batch_device picks, where that chain
+ * is kept.  Optionally d_ranked_start_out (int64, n + 1) with d_ranked_t_out / _q_out / _len_out (total_cand each; all four or none):
+ * every read's kept chains one after the other in rank order, each ascending, n_anchors of each in its record.
+ * d_status_out (optional), per read: MGL_SW_ERR_BAD_ARG for a row with d_row_q_len < 1, a row's range of d_cand_start that descends or
+ * leaves [0, total_cand], or a pred(i) outside [-1, i) or more than 64 behind i; then MGL_SW_ERR_UNSUPPORTED for a row with more than
+ * max_cand candidates.  A refused read has n_chains 0 and nothing else written.  A row whose d_row_status is not 0 contributes no
+ * chains and its f / pred are never read.  A read with no kept chain is status 0 with n_chains 0.  The candidates' t, q and l are taken
+ * as the chain stage accepted them and f as it wrote them.
+ * MGL_SW_ERR_BAD_ARG before any device work for a null required pointer, anchor outputs that are neither all given nor all null,
+ * n < 0, n * strands or total_cand above 2^30, strands outside 1, 2, max_cand outside 0 .. 8192, max_chains outside 1 .. 16,
+ * min_score < 1, min_cnt < 1 or mask_level outside 1 .. 256; MGL_SW_ERR_DEVICE without a GPU; MGL_SW_ERR_NOMEM where the workspace
+ * limit does not hold 4 bytes per read and, with the anchor outputs, 4 bytes per candidate.
+ * Device work on `stream`, no synchronisation: sw_rank_chains_kernel (a workgroup per read) and, for the anchor outputs, a prefix sum
+ * and sw_rank_pack_kernel.  No MGL_SW_KERNEL_* id: the timing record keeps its fill_kernel.
+ */
+typedef struct mgl_sw_ranked_chain {
+    int32_t score, strand, n_anchors, t_beg, t_end, q_beg, q_end, parent, n_sub, subsc, mapq, end_index;
+} mgl_sw_ranked_chain;
+
+int mgl_sw_rank_chains_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, int strands, const int32_t *d_row_q_len,
+                                    const int64_t *d_cand_start, const int32_t *d_cand_t, const int32_t *d_cand_q, const int32_t *d_cand_len,
+                                    int64_t total_cand, const int32_t *d_f, const int32_t *d_pred, const int32_t *d_row_status, int max_cand,
+                                    int max_chains, int min_score, int min_cnt, int mask_level, int32_t *d_n_chains_out,
+                                    mgl_sw_ranked_chain *d_records_out, int64_t *d_ranked_start_out, int32_t *d_ranked_t_out,
+                                    int32_t *d_ranked_q_out, int32_t *d_ranked_len_out, int32_t *d_status_out);
+
+/*
  * Logical backtrack matrix of one pair, the reference's calculateMatrix
  * (sw_scalar.h:7 / sw.cpp:5-146): btr is (tl+1)*(ql+1) int32 row-major with
  * row 0 / column 0 zero, +k = k rows up (deletion run), -k = k columns left

@@ -41,6 +41,8 @@ ChainAlignResult = namedtuple("ChainAlignResult", "score t_beg t_end q_beg q_end
 ChainAnchorsResult = namedtuple("ChainAnchorsResult", "chains score status")
 SeedResult = namedtuple("SeedResult", "candidates status")
 MapResult = namedtuple("MapResult", "ref_beg ref_end strand score cigars status")
+RankedMapResult = namedtuple("RankedMapResult", "ref_beg ref_end strand score cigars status mapq n_chains secondary")
+RankedChain = namedtuple("RankedChain", "score strand n_anchors t_beg t_end q_beg q_end parent n_sub subsc mapq end_index")
 IndexInfo = namedtuple("IndexInfo", "ref_len entries bytes k w")
 
 
@@ -790,6 +792,128 @@ class MicrosoftSmithWaterman:
         ln = np.where(ok, ln, 0).astype(np.int32)
         return MapResult(np.where(ok, t_start + rec[:, 1], 0), np.where(ok, t_start + rec[:, 2], 0), np.where(ok, strand, 0).astype(np.int32),
                          np.where(ok, rec[:, 0], 0).astype(np.int32), CigarColumn(cg, ln), np.where(wst != 0, wst, st).astype(np.int32))
+
+    def rank_chains(self, row_q_lens, candidates, f, pred, row_status=None, strands=2, max_chains=4, min_score=40, min_cnt=3, mask_level=128,
+                    max_cand=None, return_anchors=False):
+        """mgl_sw_rank_chains_batch_device over lists: ``candidates[r]`` = the (t, q, l) of row r, ``f[r]`` and ``pred[r]`` the chain
+        stage's values for them (``chain_anchors(..., return_dp=True)``), ``row_q_lens[r]`` the row's read length; read p has the rows
+        strands * p .. (tests/rank_textbook.py).  NOT a reference function.  Returns (chains, status): ``chains[p]`` the RankedChain
+        records of read p in rank order (a refused read has none; no exception for a read's status); with ``return_anchors`` also,
+        per read and chain, the chain's [(t, q, l)] ascending: (chains, anchors, status)."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        rows = len(candidates)
+        assert len(row_q_lens) == len(f) == len(pred) == rows and strands in (1, 2) and rows % strands == 0
+        start = np.zeros(rows + 1, np.int64)
+        if rows:
+            np.cumsum([len(c) for c in candidates], out=start[1:])
+        flat = np.asarray([a for c in candidates for a in c], dtype=np.int32).reshape(-1, 3)
+        cat = lambda xs: np.asarray([v for x in xs for v in x], dtype=np.int32)  # noqa: E731
+        if max_cand is None:
+            max_cand = int(np.diff(start).max(initial=0))
+        g = lambda x, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dt))).to(dev)  # noqa: E731
+        out = self.rank_chains_device(g(row_q_lens, np.int32), g(start, np.int64), g(flat[:, 0], np.int32), g(flat[:, 1], np.int32), g(flat[:, 2], np.int32),
+                                      g(cat(f), np.int32), g(cat(pred), np.int32), None if row_status is None else g(row_status, np.int32), strands, max_cand,
+                                      max_chains, min_score, min_cnt, mask_level, anchors=return_anchors)
+        torch.cuda.synchronize(dev)
+        nc, rec, rs, rt, rq, rl, st = (None if x is None else x.cpu().numpy() for x in out)
+        chains = [[RankedChain(*(int(v) for v in rec[p, c])) for c in range(nc[p])] for p in range(rows // strands)]
+        if not return_anchors:
+            return chains, st
+        anchors = []
+        for p, cs in enumerate(chains):
+            at, per = int(rs[p]), []
+            for c in cs:
+                per.append([(int(rt[i]), int(rq[i]), int(rl[i])) for i in range(at, at + c.n_anchors)])
+                at += c.n_anchors
+            anchors.append(per)
+        return chains, anchors, st
+
+    def rank_chains_device(self, row_q_len, cand_start, cand_t, cand_q, cand_len, f, pred, row_status=None, strands=2, max_cand=4096, max_chains=4,
+                           min_score=40, min_cnt=3, mask_level=128, anchors=False, out=None):
+        """The device-tensor form: the rows' tensors as ``seed_index_device`` and ``chain_anchors_device(dp=True)`` wrote them (int32;
+        int64 ``cand_start`` [rows + 1]); enqueued on the current stream, not synchronised.  Returns (n_chains [n] int32, records
+        [n, max_chains, 12] int32 -- mgl_sw_ranked_chain's fields; rows at or beyond n_chains are not written --, ranked_start [n + 1]
+        int64, ranked_t, ranked_q, ranked_len [candidates] int32 -- all four None without ``anchors`` --, status [n] int32) tensors;
+        ``out``: such a tuple to write into (its status may be None), whose anchor tensors decide whether anchors are written."""
+        import torch
+
+        ctx = self._ensure()
+        rows = int(row_q_len.numel())
+        n = rows // strands if strands in (1, 2) else rows
+        total = int(cand_t.numel())
+        dev = row_q_len.device
+        if out is None:
+            i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
+            out = (i32(n), torch.empty((n, max(int(max_chains), 0), 12), dtype=torch.int32, device=dev),
+                   torch.empty(n + 1, dtype=torch.int64, device=dev) if anchors else None, *((i32(total) if anchors else None) for _ in range(3)), i32(n))
+        nc, rec, rs, rt, rq, rl, st = out
+        assert strands not in (1, 2) or (rows % strands == 0 and cand_start.numel() >= rows + 1)
+        assert nc.numel() >= n and rec.numel() >= n * max_chains * 12 and min(cand_q.numel(), cand_len.numel(), f.numel(), pred.numel()) >= total
+        spare = torch.empty(2, dtype=torch.int64, device=dev)  # an empty tensor has no address: the entry wants one
+        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        rc = _lib.lib().mgl_sw_rank_chains_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, int(strands), ptr(row_q_len), ptr(cand_start), ptr(cand_t), ptr(cand_q), ptr(cand_len), total,
+            ptr(f), ptr(pred), ptr(row_status), int(max_cand), int(max_chains), int(min_score), int(min_cnt), int(mask_level), ptr(nc), ptr(rec), ptr(rs),
+            ptr(rt), ptr(rq), ptr(rl), ptr(st))
+        _check(rc, ctx)
+        return out
+
+    def map_reads_ranked_device(self, index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters=GATK_PARAMETERS, strands=2, max_cand=4096,
+                                cand_capacity=None, seed_out=None, chain_out=None, max_chains=4, min_score=40, min_cnt=3, mask_level=128, rank_anchors=False,
+                                rank_out=None, **stages):
+        """``map_reads_device`` with the chain stage's f and pred kept and ``rank_chains_device`` on them, on the current stream,
+        nothing read back and nothing synchronised in between: the strand choice, the window and the alignment are
+        ``map_reads_device``'s own, unchanged.  ``stages``: its further arguments.  Returns its five tuples and the ranking's:
+        (seeds, chain, chosen, window, aln, ranked).  A ranked chain's t_beg / t_end are positions of the reference as they stand,
+        its q_beg / q_end those of its strand's oriented read."""
+        import torch
+
+        n = int(q_start.numel())
+        dev = queries.device
+        if chain_out is None:  # the chain stage's tuple with f and pred in it: sized as map_reads_device sizes the seed stage's
+            rows = max(int(strands), 0) * n
+            total = int(seed_out[1].numel()) if seed_out is not None else cand_capacity if cand_capacity is not None else min(rows * int(max_cand), 1 << 30)
+            i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
+            chain_out = (torch.empty(rows + 1, dtype=torch.int64, device=dev), i32(total), i32(total), i32(total), i32(rows), i32(total), i32(total), i32(rows))
+        assert chain_out[5] is not None and chain_out[6] is not None, "chain_out needs f and pred (chain_anchors_device(dp=True))"
+        seeds, chain, chosen, window, aln = self.map_reads_device(index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters, strands=strands,
+                                                                  max_cand=max_cand, cand_capacity=cand_capacity, seed_out=seed_out, chain_out=chain_out,
+                                                                  **stages)
+        ranked = self.rank_chains_device(seeds[5], *seeds[:4], chain[5], chain[6], chain[7], strands, max_cand, max_chains, min_score, min_cnt, mask_level,
+                                         anchors=rank_anchors, out=rank_out)
+        return seeds, chain, chosen, window, aln, ranked
+
+    def map_reads_ranked(self, index, reads, band=64, zdrop=-1, parameters=GATK_PARAMETERS, slack=200, strands=2, max_tl=None, **stages):
+        """``map_reads_ranked_device`` over a list of byte strings: ``map_reads`` with a mapping quality.  Returns RankedMapResult:
+        MapResult's fields as ``map_reads`` gives them, and per read ``mapq`` (that of its first ranked chain, which is the chain
+        that was aligned; 0 for a read without ranked chains, whether it was aligned or not), ``n_chains`` and ``secondary``: the
+        ranked chains behind the first as (ref_beg, ref_end, strand, score, parent) -- parent is the rank of the primary chain it
+        is secondary to, or its own rank where it is primary on another part of the read.  They are reported, not aligned."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        qs = [bytes(q) for q in reads]
+        n, packed, _ = _pack_pairs(qs, qs, dev, 16, False)
+        max_ql = packed[7]
+        if max_tl is None:
+            max_tl = max_ql + max_ql // 2 + 2 * int(slack)
+        stride = stages.pop("cigar_stride", None) or _default_stride(max_tl, max_ql, False)
+        _, _, chosen, window, aln, ranked = self.map_reads_ranked_device(index, *packed[3:6], max_tl, max_ql, band, zdrop, parameters, strands=strands,
+                                                                         slack=slack, cigar_stride=stride, **stages)
+        torch.cuda.synchronize(dev)
+        rec, cg, ln, st = aln[0].cpu().numpy(), aln[4].cpu().numpy().reshape(n, stride), aln[5].cpu().numpy(), aln[6].cpu().numpy()
+        t_start, wst = window[0].cpu().numpy(), window[3].cpu().numpy()
+        ok = st == 0
+        strand = chosen[0].cpu().numpy() if chosen is not None else np.zeros(n, np.int32)
+        ln = np.where(ok, ln, 0).astype(np.int32)
+        nc, rr = ranked[0].cpu().numpy(), ranked[1].cpu().numpy()
+        mapq = np.asarray([int(rr[p, 0, 10]) if nc[p] > 0 else 0 for p in range(n)], dtype=np.int32)
+        secondary = [[(int(c[3]), int(c[4]), int(c[1]), int(c[0]), int(c[7])) for c in rr[p, 1:nc[p]]] for p in range(n)]
+        return RankedMapResult(np.where(ok, t_start + rec[:, 1], 0), np.where(ok, t_start + rec[:, 2], 0), np.where(ok, strand, 0).astype(np.int32),
+                               np.where(ok, rec[:, 0], 0).astype(np.int32), CigarColumn(cg, ln), np.where(wst != 0, wst, st).astype(np.int32), mapq,
+                               nc.astype(np.int32), secondary)
 
     def align_packed_2bit(self, target_bases, target_base_count, t_start, t_len, query_bases, query_base_count, q_start, q_len,
                           max_tl, max_ql, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,

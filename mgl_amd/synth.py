@@ -193,3 +193,24 @@ def mapping_set(seed, count, length=10000, spacer=3000):
     parts.append(BASES[rng.integers(4, size=spacer)].tobytes())
     reads = [revcomp(Q) if p % 2 else Q for p, (_, Q, _) in enumerate(pairs)]
     return b"".join(parts), reads, truth
+
+
+def repeat_mapping_set(seed, count, length=10000, spacer=3000, copies=0, divergence=0.0):
+    """``mapping_set(seed, count, length, spacer)`` on a reference with repeats: the windows of the first ``copies`` reads appended
+    once more to the reference, each with its bases substituted (by another base) at rate ``divergence`` and followed by ``spacer``
+    random bases.  The reads and the truth are ``mapping_set``'s: the true place of a read is its first copy.
+    -> (ref, reads, truth, copy), copy[p] = (the position of the second copy of T_p in ref, len(T_p)) for p < copies."""
+    ref, reads, truth = mapping_set(seed, count, length, spacer)
+    assert 0 <= copies <= count and 0.0 <= divergence <= 1.0
+    rng = np.random.default_rng([seed, count, length, spacer, copies, int(round(divergence * 1e6))])
+    parts, copy, at = [ref], [], len(ref)
+    for pos, n, _ in truth[:copies]:
+        w = np.frombuffer(ref[pos:pos + n], np.uint8).copy()
+        hit = np.flatnonzero(rng.random(n) < divergence)
+        code = np.searchsorted(BASES, w[hit])
+        w[hit] = BASES[(code + rng.integers(1, 4, size=len(hit))) % 4]
+        copy.append((at, n))
+        parts.append(w.tobytes())
+        parts.append(BASES[rng.integers(4, size=spacer)].tobytes())
+        at += n + spacer
+    return b"".join(parts), reads, truth, copy
