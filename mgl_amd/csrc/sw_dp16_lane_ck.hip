@@ -135,7 +135,7 @@ struct SeqBlocks {
 // the wave's arrays (every pointer includes the lane): what pass 1 keeps, time-major -- a lane only ever reads what it wrote itself
 struct WaveMem {
     uint2 *bnd;    // [row 32 k, k = 0 .. strips][column 0 .. ql][lane] {H, E} packed A | B: the carry row entering strip k (row 0: the border)
-    uint2 *mid;    // [strip][column 1 .. ql][lane]: the row in the strip's middle (row 32 k + 16)
+    uint2 *mid;    // [strip][column 1 .. ql][lane]: the row in the strip's middle (row 32 k + 16)   (bnd, mid, ck: the WIDE form; NARROW: below)
     unsigned *ck;  // [strip][block 1 .. nb - 1][2 r | 2 r + 1][lane]: H[.][32 b] and the horizontal-gap value of the strip's row r entering column 32 b + 1
     uint4 *blk;    // [column of the block][lane]: the recomputed flags of 16 rows
     // the same arrays as pass 2 addresses them: wave-uniform bases (SGPRs) and 32-bit indices that include the lane -- one address
@@ -157,44 +157,48 @@ struct WaveMem {
     // fo = max(hn - (o-e), fr) with hn >= fr, so H - E of a kept row and H - (gap value) of a checkpoint lie in [0, o-e] in every cell
     // that does not wrap: where o - e <= 255 the second value of a record is H minus ONE BYTE, and a lane keeps the H of four columns
     // (rows) as one 16-byte vector.  Same region, same bases of bnd / mid / ck / blk; the records use less of the parts they replace:
-    //   mid   strip k still starts at entry k ql 64 of `mid` (512 ql bytes per strip).  Its columns go in groups of four, group g =
-    //         columns 4 g + 1 .. 4 g + 4, 1 536 bytes each: [lane] uint4 H of the four columns | [lane] uint2 the differences H - E, byte
-    //         2 u of the uint2 pair A's of column 4 g + 1 + u, byte 2 u + 1 pair B's.  A last group of THREE columns is written the same
-    //         way (its fourth column holds nothing anybody reads); a last group of one or two columns keeps the wide records, [column]
-    //         [lane] uint2 {H, E}, where the group starts (mid_tail_wide).  So four columns take 1 536 bytes of their 2 048, three all
-    //         of their 1 536, one or two their own 512 each: a strip never leaves its 512 ql bytes, whatever ql is (written whole,
-    //         the groups would: 3 ceil(ql / 4) <= ql fails for ql = 1, 2 and 5).
+    //   rows  EVERY kept row -- the carry row entering strip k (row 32 k; row 0: the border) and the row in a strip's middle (row
+    //         32 k + 16) -- has one format and keeps its place: carry row k starts at entry k (ql + 1) 64 of `bnd` (512 (ql + 1) bytes),
+    //         the middle row of strip k at entry k ql 64 of `mid` (512 ql bytes): kept_row_off.  Column 0 is not stored (a formula).  The
+    //         columns go in groups of four, group g = columns 4 g + 1 .. 4 g + 4, 1 536 bytes each: [lane] uint4 H of the four columns |
+    //         [lane] uint2 the differences H - E, byte 2 u of the uint2 pair A's of column 4 g + 1 + u, byte 2 u + 1 pair B's.  A last
+    //         group of one to three columns is written the same way (its other columns hold nothing anybody reads) wherever whole
+    //         groups fit a middle row's bytes, 3 ceil(ql / 4) <= ql: every ql but 1, 2 and 5.  For those three the last group keeps
+    //         the wide records, [column][lane] uint2 {H, E}, where the group starts (tail_wide: ql is the wave's, so this is a
+    //         property of the WAVE).  The narrow kernels never store the last row.
     //   ck    checkpoint (strip, block) still starts at dword ((strip (nb - 1) + block - 1) 64) 64 of `ck` (16 KB each) and is twelve
     //         [lane] uint4: 0 .. 7 = H of rows 4 x .. 4 x + 3, 8 .. 11 = the differences H - (gap value) of rows 8 x .. 8 x + 7, two bytes
     //         per row (A, B): 12 KB of the 16.
-    // The carry rows (bnd) are the wide {H, E} in either form.
-    __device__ __forceinline__ static bool mid_tail_wide(int ql, int j) { return ((j - 1) >> 2) == (ql >> 2) && (ql & 3) != 3; } // (ql & 3 = 0: no such j)
-    template <bool NARROW>
-    __device__ __forceinline__ unsigned mid_byte_off(int strip, int ql, int j) const // H of column j (>= 1) in the strip's middle row
+    __device__ __forceinline__ static bool tail_wide(int ql) { return 3 * ((ql + 3) >> 2) > ql; } // ql = 1, 2, 5
+    // where kept row 16 m starts (bytes from `rows`): ONE formula for carry rows (m even) and middle rows (m odd)
+    __device__ __forceinline__ unsigned kept_row_off(int m, int ql) const { return (unsigned)((m >> 1) * ((ql + 1 - (m & 1)) * 512)) + (unsigned)(m & 1) * (8u * mid_off); }
+    // H of column j (>= 1) of kept row 16 m; `wide`: the column stands in a last group of wide records
+    __device__ __forceinline__ unsigned kept_h_off(int m, int ql, int j, bool &wide) const
     {
-        if (!NARROW) return 8u * (mid_off + (unsigned)((strip * ql + j - 1) * 64) + lane);
         const int c = j - 1;
-        const unsigned group = 8u * mid_off + (unsigned)(strip * ql * 512 + (c >> 2) * 1536);
-        return group + (mid_tail_wide(ql, j) ? (unsigned)((c & 3) * 512) + 8u * lane : (unsigned)((c & 3) * 4) + 16u * lane);
+        const unsigned group = kept_row_off(m, ql) + (unsigned)((c >> 2) * 1536);
+        wide = tail_wide(ql) && (c >> 2) == ((ql - 1) >> 2);
+        return group + (wide ? (unsigned)((c & 3) * 512) + 8u * lane : (unsigned)((c & 3) * 4) + 16u * lane);
     }
     template <bool NARROW>
-    __device__ __forceinline__ unsigned row16_h(int m, int ql, int j) const // H alone of row 16 m at column j, both pairs
+    __device__ __forceinline__ unsigned row16_h(int m, int ql, int j) const // H alone of row 16 m at column j (>= 1), both pairs
     {
         if (!NARROW) return row16(m, ql, j).x; // (the wide kernels: the code they had before there were two forms)
-        return at32<unsigned>(rows, (m & 1) ? mid_byte_off<true>(m >> 1, ql, j) : 8u * ((unsigned)(((m >> 1) * (ql + 1) + j) * 64) + lane));
+        bool wide;
+        return at32<unsigned>(rows, kept_h_off(m, ql, j, wide));
     }
-    // {H, E} of row 16 m at column j in two dword loads whose addresses are selected, not branched on (m differs from lane to lane)
+    // {H, E} of row 16 m at column j (>= 1), one column at a time (NARROW: what ck_block falls back to where the wave has a wide tail)
     template <bool NARROW>
     __device__ __forceinline__ uint2 row16_n(int m, int ql, int j) const
     {
         if (!NARROW) return row16(m, ql, j);
         const int c = j - 1;
-        const bool bytes = (m & 1) != 0 && !mid_tail_wide(ql, j); // E is H minus a byte (else: the record's second dword)
-        const unsigned hoff = (m & 1) ? mid_byte_off<true>(m >> 1, ql, j) : 8u * ((unsigned)(((m >> 1) * (ql + 1) + j) * 64) + lane);
-        const unsigned soff = bytes ? 8u * mid_off + (unsigned)((m >> 1) * ql * 512 + (c >> 2) * 1536 + 1024 + ((c >> 1) & 1) * 4) + 8u * lane : hoff + 4u;
+        bool wide;
+        const unsigned hoff = kept_h_off(m, ql, j, wide);
+        const unsigned soff = wide ? hoff + 4u : kept_row_off(m, ql) + (unsigned)((c >> 2) * 1536 + 1024 + ((c >> 1) & 1) * 4) + 8u * lane;
         const unsigned hv = at32<unsigned>(rows, hoff), sv = at32<unsigned>(rows, soff);
         const unsigned d = __builtin_amdgcn_perm(0u, sv, (c & 1) ? 0x0c030c02u : 0x0c010c00u); // ZERO-extended: a difference reaches 255
-        return make_uint2(hv, bytes ? pk_sub(hv, d) : sv);
+        return make_uint2(hv, wide ? sv : pk_sub(hv, d));
     }
     __device__ __forceinline__ unsigned qblock(int blk4, int half) const { return at32<unsigned>(seq, 4u * ((unsigned)((2 * blk4 + half) * 64) + lane)); }
     __device__ __forceinline__ unsigned tblock(int blk4, int half) const { return at32<unsigned>(seq, 4u * (t_off + (unsigned)((2 * blk4 + half) * 64) + lane)); }
@@ -646,14 +650,31 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
     // lane offsets -- the two record sizes of a group as two POINTERS that include the lane were four registers and spilled in the loops
     char *mg = reinterpret_cast<char *>(const_cast<uint2 *>(wm.rows)) + (size_t)8 * wm.mid_off + (size_t)k * ql * 512;
     char *cg = reinterpret_cast<char *>(const_cast<unsigned *>(wm.cku)) + (size_t)k * (nb - 1) * 16384;
-    const unsigned l16 = 16u * wm.lane, l8 = 8u * wm.lane;
+    // ... and the groups of the carry rows (WaveMem: every kept row has the middle rows' format): `ig` the row entering the strip, `og`
+    // the row leaving it
+    const char *ig = reinterpret_cast<const char *>(wm.rows) + (size_t)k * (ql + 1) * 512;
+    char *og = reinterpret_cast<char *>(const_cast<uint2 *>(wm.rows)) + (size_t)(k + 1) * (ql + 1) * 512;
+    const bool tail_wide = WaveMem::tail_wide(ql); // (wave-uniform: the last group of one or two columns keeps the wide records)
+    unsigned l16 = 16u * wm.lane, l8 = 8u * wm.lane;
+    // (NARROW: the strip's own copies.  A wave keeps its slot, so base + lane offset of every array is invariant in the kernel's tile
+    // loop: computed once in front of it, each a register pair, and with the carry rows' two more than the registers hold -- kept in
+    // scratch for the kernel's whole life.  Two adds per strip instead.)
+    if (NARROW) asm volatile("" : "+v"(l16), "+v"(l8));
     unsigned mh[4] = {0u, 0u, 0u, 0u}, md0 = 0u, md[2] = {0u, 0u}; // NARROW: the group's four H and its difference bytes so far
-    unsigned me[2] = {0u, 0u};                                     // ... and E of its first two columns (a last group of one or two: wide records)
+    unsigned me[2] = {0u, 0u};                                     // ... and E of its first two columns (a last group of wide records)
+    unsigned ch[4] = {0u, 0u, 0u, 0u}, cd0 = 0u, cd[2] = {0u, 0u}, ce[2] = {0u, 0u}; // the same of the row that leaves the strip
     unsigned *ckp = wm.ck + (size_t)k * (nb - 1) * 64 * 64;
-    unsigned hd = bp[-64].x; // H[32 k][0]
+    unsigned hd; // H[32 k][0]
+    if (NARROW) { // (column 0 of a kept row is not stored: the border's formula, as in `column 0` above)
+        const int hb = border(i0, gopen, gext, indel) + i0 * gext + base;
+        hd = pack2(hb, hb);
+    } else {
+        hd = bp[-64].x;
+    }
     // column u (0 .. 3) of the group whose query dwords are qa / qb
     int j = 1;
-    auto one_column = [&](const uint2 top, const unsigned qa, const unsigned qb, const int u) {
+    // (tail: a column of the last, partial group -- only there E of a kept cell may leave as a wide record's second dword)
+    auto one_column = [&](const uint2 top, const unsigned qa, const unsigned qb, const int u, const bool tail = false) {
         unsigned e = top.y;
         uint2 mid;
         if (CODES)
@@ -663,7 +684,7 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
         hd = top.x;
         if (NARROW) { // (stored once per group: mid_group below)
             mh[u] = mid.x;
-            if (u < 2) me[u] = mid.y;
+            if (tail && u < 2) me[u] = mid.y;
             const unsigned d = pk_sub(mid.x, mid.y);
             if (u & 1)
                 md[u >> 1] = __builtin_amdgcn_perm(d, md0, 0x06040200u); // bytes {A, B} of column u - 1, {A, B} of column u
@@ -673,9 +694,20 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
             if (!(MGL_CK_ABLATE & 4)) mp[0] = mid;
             mp += 64;
         }
-        if (LAST == NOT_LAST) {
+        if (NARROW) { // the row that leaves the strip: once per group as well (carry_group below); the last strip's is never stored
+            if (LAST == NOT_LAST) {
+                ch[u] = h[R - 1];
+                if (tail && u < 2) ce[u] = e;
+                const unsigned d = pk_sub(h[R - 1], e);
+                if (u & 1)
+                    cd[u >> 1] = __builtin_amdgcn_perm(d, cd0, 0x06040200u);
+                else
+                    cd0 = d;
+            }
+        } else if (LAST == NOT_LAST) {
             bo[0] = make_uint2(h[R - 1], e);
-        } else { // H[tl][j]
+        }
+        if (LAST != NOT_LAST) { // H[tl][j]
             unsigned bot = h[R - 1];
             if (rl != R - 1) {
 #pragma unroll
@@ -692,13 +724,19 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
         }
         if (LAST != LAST_ROW_KEYS) bo += 64;
     };
-    auto mid_group = [&](const int cols) { // NARROW: the group's `cols` columns (3 or 4) leave in two stores
-        if (cols == 3) md[1] = __builtin_amdgcn_perm(md0, md0, 0x06040200u); // (the third column's bytes wait in md0 for a neighbour)
+    auto mid_group = [&](const int cols) { // NARROW: the group's `cols` columns (1 .. 4) leave in two stores
+        if (cols & 1) md[cols >> 1] = __builtin_amdgcn_perm(md0, md0, 0x06040200u); // (an odd column's bytes wait in md0 for a neighbour)
         if (!(MGL_CK_ABLATE & 4)) {
             *reinterpret_cast<uint4 *>(mg + l16) = make_uint4(mh[0], mh[1], mh[2], mh[3]);
             *reinterpret_cast<uint2 *>(mg + 1024 + l8) = make_uint2(md[0], md[1]);
         }
         mg += 1536;
+    };
+    auto carry_group = [&](const int cols) { // ... and so does the row that leaves the strip (NARROW, LAST == NOT_LAST)
+        if (cols & 1) cd[cols >> 1] = __builtin_amdgcn_perm(cd0, cd0, 0x06040200u);
+        *reinterpret_cast<uint4 *>(og + l16) = make_uint4(ch[0], ch[1], ch[2], ch[3]);
+        *reinterpret_cast<uint2 *>(og + 1024 + l8) = make_uint2(cd[0], cd[1]);
+        og += 1536;
     };
     auto save = [&]() { // the state BEFORE column j: H[.][j-1] and the horizontal-gap values entering column j
         if (NARROW) {
@@ -728,39 +766,94 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
     // group before it, so its latency -- and the acknowledgements of the stores issued in between, which s_waitcnt vmcnt counts
     // in the same queue -- hides behind a thousand instructions of arithmetic instead of stalling the wave at every group (measured
     // before: a third of the waves' lifetime in s_waitcnt at two waves per SIMD).  Reads past column ql stay inside the wave's own
-    // region (the next kept row follows) and are never used.
-    uint2 n0 = bp[0], n1 = bp[64], n2 = bp[128], n3 = bp[192];
-    unsigned nqa = qst[0], nqb = qst[64];
-    for (; j + 3 <= ql; j += 4) {
-        if (!(MGL_CK_ABLATE & 2) && j > 1 && ((j - 1) & (CK - 1)) == 0) save(); // (column 0 is a formula: no checkpoint)
-        const uint2 top0 = n0, top1 = n1, top2 = n2, top3 = n3;
-        const unsigned qa = nqa, qb = nqb;
-        qst += 128;
-        bp += 256;
-        n0 = bp[0];
-        n1 = bp[64];
-        n2 = bp[128];
-        n3 = bp[192];
-        nqa = qst[0];
-        nqb = qst[64];
-        one_column(top0, qa, qb, 0);
-        one_column(top1, qa, qb, 1);
-        one_column(top2, qa, qb, 2);
-        one_column(top3, qa, qb, 3);
-        if (NARROW) mid_group(4);
-    }
-    if (j <= ql) { // the last one to three columns (j - 1 is a multiple of four here)
-        if (j > 1 && ((j - 1) & (CK - 1)) == 0) save();
-        one_column(n0, nqa, nqb, 0);
-        if (j + 1 <= ql) one_column(n1, nqa, nqb, 1);
-        if (j + 2 <= ql) one_column(n2, nqa, nqb, 2);
-        if (NARROW) { // (WaveMem: a last group of three as every group, of one or two as wide records)
-            if (j + 2 <= ql) {
-                mid_group(3);
-            } else if (!(MGL_CK_ABLATE & 4)) {
-                *reinterpret_cast<uint2 *>(mg + l8) = make_uint2(mh[0], me[0]);
-                if (j + 1 <= ql) *reinterpret_cast<uint2 *>(mg + 512 + l8) = make_uint2(mh[1], me[1]);
+    // region (the next kept row follows; the narrow kernels' last carry row, "entering strip `strips`", is allocated and never
+    // written) and are never used.
+    if (NARROW) {
+        // the group's H as one 16-byte vector and its difference bytes as one 8-byte vector; E of a column is H minus its zero-extended
+        // byte.  (A wave with a wide tail, ql = 1, 2, 5, fetches a narrow group where its tail stands -- inside the row, not used -- and
+        // its two wide records below, in front of the tail's columns: the only load of pass 1 that is waited for where it is issued,
+        // once per strip of a query of at most five columns.  Fetched a group ahead they would be four more registers live through
+        // every wave's loop, or a branch at every group's loads.)
+        uint4 nh;
+        uint2 nd;
+        auto fetch = [&]() {
+            nh = *reinterpret_cast<const uint4 *>(ig + l16);
+            nd = *reinterpret_cast<const uint2 *>(ig + 1024 + l8);
+            ig += 1536;
+        };
+        auto top = [&](const uint4 th, const uint2 td, const int u) {
+            const unsigned hv = u == 0 ? th.x : u == 1 ? th.y : u == 2 ? th.z : th.w;
+            const unsigned d = __builtin_amdgcn_perm(0u, u < 2 ? td.x : td.y, (u & 1) ? 0x0c030c02u : 0x0c010c00u); // ZERO-extended
+            return make_uint2(hv, pk_sub(hv, d));
+        };
+        fetch();
+        unsigned nqa = qst[0], nqb = qst[64];
+        for (; j + 3 <= ql; j += 4) {
+            if (!(MGL_CK_ABLATE & 2) && j > 1 && ((j - 1) & (CK - 1)) == 0) save(); // (column 0 is a formula: no checkpoint)
+            const uint4 th = nh;
+            const uint2 td = nd;
+            const unsigned qa = nqa, qb = nqb;
+            qst += 128;
+            fetch();
+            nqa = qst[0];
+            nqb = qst[64];
+            one_column(top(th, td, 0), qa, qb, 0);
+            one_column(top(th, td, 1), qa, qb, 1);
+            one_column(top(th, td, 2), qa, qb, 2);
+            one_column(top(th, td, 3), qa, qb, 3);
+            mid_group(4);
+            if (LAST == NOT_LAST) carry_group(4);
+        }
+        if (j <= ql) { // the last one to three columns (j - 1 is a multiple of four here)
+            if (j > 1 && ((j - 1) & (CK - 1)) == 0) save();
+            const int cols = ql - j + 1;
+            uint2 t0 = top(nh, nd, 0), t1 = top(nh, nd, 1);
+            if (tail_wide) { // one or two columns as wide records, where the group starts (`ig` has moved past it)
+                t0 = *reinterpret_cast<const uint2 *>(ig - 1536 + l8);
+                t1 = *reinterpret_cast<const uint2 *>(ig - 1024 + l8);
             }
+            one_column(t0, nqa, nqb, 0, true);
+            if (cols >= 2) one_column(t1, nqa, nqb, 1, true);
+            if (cols >= 3) one_column(top(nh, nd, 2), nqa, nqb, 2, true);
+            if (!tail_wide) { // a whole group like every other; the columns past ql hold nothing anybody reads
+                mid_group(cols);
+                if (LAST == NOT_LAST) carry_group(cols);
+            } else {
+                if (!(MGL_CK_ABLATE & 4)) {
+                    *reinterpret_cast<uint2 *>(mg + l8) = make_uint2(mh[0], me[0]);
+                    if (cols >= 2) *reinterpret_cast<uint2 *>(mg + 512 + l8) = make_uint2(mh[1], me[1]);
+                }
+                if (LAST == NOT_LAST) {
+                    *reinterpret_cast<uint2 *>(og + l8) = make_uint2(ch[0], ce[0]);
+                    if (cols >= 2) *reinterpret_cast<uint2 *>(og + 512 + l8) = make_uint2(ch[1], ce[1]);
+                }
+            }
+        }
+    } else {
+        uint2 n0 = bp[0], n1 = bp[64], n2 = bp[128], n3 = bp[192];
+        unsigned nqa = qst[0], nqb = qst[64];
+        for (; j + 3 <= ql; j += 4) {
+            if (!(MGL_CK_ABLATE & 2) && j > 1 && ((j - 1) & (CK - 1)) == 0) save(); // (column 0 is a formula: no checkpoint)
+            const uint2 top0 = n0, top1 = n1, top2 = n2, top3 = n3;
+            const unsigned qa = nqa, qb = nqb;
+            qst += 128;
+            bp += 256;
+            n0 = bp[0];
+            n1 = bp[64];
+            n2 = bp[128];
+            n3 = bp[192];
+            nqa = qst[0];
+            nqb = qst[64];
+            one_column(top0, qa, qb, 0);
+            one_column(top1, qa, qb, 1);
+            one_column(top2, qa, qb, 2);
+            one_column(top3, qa, qb, 3);
+        }
+        if (j <= ql) { // the last one to three columns (j - 1 is a multiple of four here)
+            if (j > 1 && ((j - 1) & (CK - 1)) == 0) save();
+            one_column(n0, nqa, nqb, 0);
+            if (j + 1 <= ql) one_column(n1, nqa, nqb, 1);
+            if (j + 2 <= ql) one_column(n2, nqa, nqb, 2);
         }
     }
     if (LAST != NOT_LAST) { // H[tl][ql], where the walks of the non-softclip strategies start
@@ -877,14 +970,15 @@ __device__ __forceinline__ void ck_block(const int sA, const int bA, const int s
     unsigned hd;
     {
         unsigned a0 = 0u, b0 = 0u; // H[16 s][CK b]
-        if (needA) a0 = wm.row16_h<NARROW>(sA, g.ql, CK * bA);
-        if (needB) b0 = wm.row16_h<NARROW>(sB, g.ql, CK * bB);
-        if (sA & 1) { // (the middle rows start at column 1: column 0 by its formula)
+        // (NARROW: no kept row stores column 0 -- the load is of column 1 then, some valid entry that is not used)
+        if (needA) a0 = wm.row16_h<NARROW>(sA, g.ql, NARROW ? max(CK * bA, 1) : CK * bA);
+        if (needB) b0 = wm.row16_h<NARROW>(sB, g.ql, NARROW ? max(CK * bB, 1) : CK * bB);
+        if (NARROW || (sA & 1)) { // (the middle rows start at column 1: column 0 by its formula)
             const int row = sA * RB;
             const int v = border(row, g.gopen, g.gext, g.indel) + row * g.gext + g.base;
             a0 = bA > 0 ? a0 : (unsigned)v;
         }
-        if (sB & 1) {
+        if (NARROW || (sB & 1)) {
             const int row = sB * RB;
             const int v = border(row, g.gopen, g.gext, g.indel) + row * g.gext + g.base;
             b0 = bB > 0 ? b0 : (unsigned)v << 16;
@@ -892,35 +986,111 @@ __device__ __forceinline__ void ck_block(const int sA, const int bA, const int s
         hd = lo_hi(a0, b0);
     }
     const int qmax = ((g.ql + 3) >> 2) - 1;
+    if (!NARROW) {
 #pragma unroll 1
-    for (int gg = 0; gg < groups; ++gg) { // (groups of eight columns, up to the last one a waiting walk stands in: it only ever moves left and up)
-        uint2 va[8], vb[8];
+        for (int gg = 0; gg < groups; ++gg) { // (groups of eight columns, up to the last one a waiting walk stands in: it only ever moves left and up)
+            uint2 va[8], vb[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) va[u] = vb[u] = make_uint2(0u, 0u);
-        if (needA) {
+            for (int u = 0; u < 8; ++u) va[u] = vb[u] = make_uint2(0u, 0u);
+            if (needA) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) va[u] = wm.row16_n<NARROW>(sA, g.ql, min(CK * bA + 8 * gg + u + 1, g.ql)); // (past ql: the last column again -- flags never read)
+                for (int u = 0; u < 8; ++u) va[u] = wm.row16_n<NARROW>(sA, g.ql, min(CK * bA + 8 * gg + u + 1, g.ql)); // (past ql: the last column again -- flags never read)
+            }
+            if (needB) {
+#pragma unroll
+                for (int u = 0; u < 8; ++u) vb[u] = wm.row16_n<NARROW>(sB, g.ql, min(CK * bB + 8 * gg + u + 1, g.ql));
+            }
+            unsigned qa[2], qb[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                qa[u] = wm.qblock(min(bA * (CK / 4) + 2 * gg + u, qmax), 0);
+                qb[u] = wm.qblock(min(bB * (CK / 4) + 2 * gg + u, qmax), 1);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                unsigned e = lo_hi(va[u].y, vb[u].y);
+                uint4 *const out = wm.blk + (size_t)(8 * gg + u) * 64;
+                if (CODES)
+                    column<RB, false, false, CODES>(h, f, t, code_table((qa[u >> 2] >> (8 * (u & 3))) & 0xffu, c.bm, c.bx), hd, e, c, out, nullptr,
+                                                    code_table((qb[u >> 2] >> (8 * (u & 3))) & 0xffu, c.bm, c.bx));
+                else
+                    column<RB, false, false, false>(h, f, t, __builtin_amdgcn_perm(qb[u >> 2], qa[u >> 2], 0x0c040c00u + 0x00010001u * (u & 3)), hd, e, c, out);
+                hd = lo_hi(va[u].x, vb[u].x);
+            }
         }
-        if (needB) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) vb[u] = wm.row16_n<NARROW>(sB, g.ql, min(CK * bB + 8 * gg + u + 1, g.ql));
-        }
+        return;
+    }
+    // NARROW
+#pragma unroll 1
+    for (int gg = 0; gg < groups; ++gg) {
+        // the round's eight columns of the kept row: hx[u] = H of {pair A, pair B}, ex[u] = E
+        unsigned hx[8], ex[8];
         unsigned qa[2], qb[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             qa[u] = wm.qblock(min(bA * (CK / 4) + 2 * gg + u, qmax), 0);
             qb[u] = wm.qblock(min(bB * (CK / 4) + 2 * gg + u, qmax), 1);
         }
+        if (!WaveMem::tail_wide(g.ql)) {
+            // every kept row has one format and a block's columns start a group: per pair two uint4 of H and two uint2 of difference
+            // bytes, whatever the band's parity.  A group past the last repeats the last one (flags never read).
+            uint4 ha[2], hb[2];
+            uint2 da[2], db[2];
+#pragma unroll
+            for (int x = 0; x < 2; ++x) {
+                ha[x] = hb[x] = make_uint4(0u, 0u, 0u, 0u);
+                da[x] = db[x] = make_uint2(0u, 0u);
+            }
+            const int glast = (g.ql - 1) >> 2;
+            if (needA) {
+                const unsigned row = wm.kept_row_off(sA, g.ql);
+#pragma unroll
+                for (int x = 0; x < 2; ++x) {
+                    const unsigned grp = row + (unsigned)(min(bA * (CK / 4) + 2 * gg + x, glast) * 1536);
+                    ha[x] = WaveMem::at32<uint4>(wm.rows, grp + 16u * wm.lane);
+                    da[x] = WaveMem::at32<uint2>(wm.rows, grp + 1024u + 8u * wm.lane);
+                }
+            }
+            if (needB) {
+                const unsigned row = wm.kept_row_off(sB, g.ql);
+#pragma unroll
+                for (int x = 0; x < 2; ++x) {
+                    const unsigned grp = row + (unsigned)(min(bB * (CK / 4) + 2 * gg + x, glast) * 1536);
+                    hb[x] = WaveMem::at32<uint4>(wm.rows, grp + 16u * wm.lane);
+                    db[x] = WaveMem::at32<uint2>(wm.rows, grp + 1024u + 8u * wm.lane);
+                }
+            }
+#pragma unroll
+            for (int x = 0; x < 2; ++x) {
+                const unsigned a4[4] = {ha[x].x, ha[x].y, ha[x].z, ha[x].w}, b4[4] = {hb[x].x, hb[x].y, hb[x].z, hb[x].w};
+                const unsigned ad[2] = {da[x].x, da[x].y}, bd[2] = {db[x].x, db[x].y};
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    hx[4 * x + u] = lo_hi(a4[u], b4[u]);
+                    // pair A's byte of its own row's dword, pair B's of its own, ZERO-extended into the two halves
+                    ex[4 * x + u] = pk_sub(hx[4 * x + u], __builtin_amdgcn_perm(bd[u >> 1], ad[u >> 1], (u & 1) ? 0x0c070c02u : 0x0c050c00u));
+                }
+            }
+        } else { // a wave with a wide tail (ql = 1, 2, 5): column by column
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                uint2 va = make_uint2(0u, 0u), vb = make_uint2(0u, 0u);
+                if (needA) va = wm.row16_n<true>(sA, g.ql, min(CK * bA + 8 * gg + u + 1, g.ql));
+                if (needB) vb = wm.row16_n<true>(sB, g.ql, min(CK * bB + 8 * gg + u + 1, g.ql));
+                hx[u] = lo_hi(va.x, vb.x);
+                ex[u] = lo_hi(va.y, vb.y);
+            }
+        }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-            unsigned e = lo_hi(va[u].y, vb[u].y);
+            unsigned e = ex[u];
             uint4 *const out = wm.blk + (size_t)(8 * gg + u) * 64;
             if (CODES)
                 column<RB, false, false, CODES>(h, f, t, code_table((qa[u >> 2] >> (8 * (u & 3))) & 0xffu, c.bm, c.bx), hd, e, c, out, nullptr,
                                                 code_table((qb[u >> 2] >> (8 * (u & 3))) & 0xffu, c.bm, c.bx));
             else
                 column<RB, false, false, false>(h, f, t, __builtin_amdgcn_perm(qb[u >> 2], qa[u >> 2], 0x0c040c00u + 0x00010001u * (u & 3)), hd, e, c, out);
-            hd = lo_hi(va[u].x, vb[u].x);
+            hd = hx[u];
         }
     }
 }
@@ -1137,7 +1307,29 @@ __device__ __forceinline__ void sw_dp16_lane_ck_tile(const DpArgs &a, const TbAr
         // 1 .. ql of the rows they leave), so a wave of a launch with ONE geometry writes them in front of its first tile only
         // (`first`) -- once per LAUNCH: the next launch on this region may have another geometry, strategy or gap cost.  A grouped
         // launch's geometry changes from tile to tile.
-        if (grouped || first) {
+        if (NARROW && (grouped || first)) {
+            // row 0 (the border row, sw.cpp:14-18,31-35) in the kept rows' one format (WaveMem): H[0][j] of a group's four columns, and
+            // E[1][j] = H[0][j] - o as the byte o - e of every column.  Column 0 of no kept row is stored.
+            char *rg = reinterpret_cast<char *>(const_cast<uint2 *>(wm.rows));
+            const int groups = (ql + 3) >> 2;
+            const unsigned bytes = (unsigned)(gopen - gext) * 0x01010101u;
+            for (int gi = 0; gi < groups; ++gi, rg += 1536) {
+                unsigned hp[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { // (columns past ql: the formula goes on, nobody reads them)
+                    const int j = 4 * gi + 1 + u, hb0 = border(j, gopen, gext, indel) + j * gext + base;
+                    hp[u] = pack2(hb0, hb0);
+                }
+                if (WaveMem::tail_wide(ql) && gi == groups - 1) { // a last group of one or two columns: wide records
+                    *reinterpret_cast<uint2 *>(rg + 8u * (unsigned)lane) = make_uint2(hp[0], pk_sub(hp[0], c.o_e));
+                    if (4 * gi + 2 <= ql) *reinterpret_cast<uint2 *>(rg + 512 + 8u * (unsigned)lane) = make_uint2(hp[1], pk_sub(hp[1], c.o_e));
+                } else {
+                    *reinterpret_cast<uint4 *>(rg + 16u * (unsigned)lane) = make_uint4(hp[0], hp[1], hp[2], hp[3]);
+                    *reinterpret_cast<uint2 *>(rg + 1024 + 8u * (unsigned)lane) = make_uint2(bytes, bytes);
+                }
+            }
+        }
+        if (!NARROW && (grouped || first)) {
             // row 0 (the border row, sw.cpp:14-18,31-35) in stored form: H[0][j], E[1][j] = H[0][j] - o
             for (int j = 0; j <= ql; ++j) {
                 const int hb0 = border(j, gopen, gext, indel) + j * gext + base;
@@ -1572,8 +1764,8 @@ __global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_kernel(const DpArgs a, 
 __global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_scatter_kernel(const DpArgs a, const TbArgs walk) { lane_ck_grid<false, false, false>(a, walk, nullptr); }
 
 // ... the twins for parameters with a folded diagonal (a.fold_k != 0, sw_device.h: diag_fold): the base-code waves form the diagonal
-// in one v_pk_mad_u16 (sw_lane_cell.h, CMP_FOLD) -- and keep pass 1's middle rows and checkpoints as the NARROW records (WaveMem;
-// launch_dp16_lane_ck sends them only launches whose o - e is a byte)
+// in one v_pk_mad_u16 (sw_lane_cell.h, CMP_FOLD) -- and keep pass 1's kept rows (carry and middle rows alike) and checkpoints as the
+// NARROW records (WaveMem; launch_dp16_lane_ck sends them only launches whose o - e is a byte)
 __global__ __launch_bounds__(64, 2) void sw_dp16_lane_ck_kernel_fold(const DpArgs a, const TbArgs walk)
 {
     __shared__ __attribute__((aligned(16))) unsigned char out_lds[LANE_CK_OUT_LDS_BYTES];
