@@ -960,6 +960,51 @@ int mgl_sw_rank_chains_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, in
                                     int32_t *d_ranked_q_out, int32_t *d_ranked_len_out, int32_t *d_status_out);
 
 /*
+ * DESCRIBING ALIGNMENTS (NOT a reference function; opt-in): behind mgl_sw_align_chain_batch_device or
+ * mgl_sw_extend_seed_batch_device, on the same stream, with no copy and no synchronisation in between.  What a SAM or PAF record
+ * needs beyond the M / I / D CIGAR: matches, mismatches, inserted and deleted bases and runs, the MD text and the extended (= / X)
+ * CIGAR.  Defined by tests/describe_textbook.py; DESIGN.md section 9l.
+ * The first ten arguments and (d_cigar, cigar_stride, d_cigar_len) are what those entries took and wrote; mgl_sw_seed_alignment has the
+ * layout of mgl_sw_chain_alignment, so the records of either go in.  Of a record only t_beg, t_end, q_beg, q_end are read.  The spans
+ * compared are T[t_start + t_beg .. t_start + t_end) and Q[q_start + q_beg .. q_start + q_end), as BYTES: no case folding, no special
+ * N -- the kernels only test equality.
+ * Counts: n_match / n_mismatch over M columns; n_ins / n_del bases; n_ins_runs / n_del_runs elements.  NM = n_mismatch + n_ins + n_del,
+ * a PAF line's block length = n_match + NM.
+ * MD (SAM specification): a decimal run of matches, 0 where there is none; a mismatch column gives the TARGET byte and the next run; a
+ * D element gives ^, its target bytes and the next run; an I element gives nothing and does not break a run; the text ends with a run
+ * (the empty alignment: "0").  Extended CIGAR: every M element split into maximal = and X runs, I and D as they are, adjacent equal
+ * operations merged across element borders.
+ * flags: MGL_SW_FLAG_BINARY_CIGAR alone is read: the input CIGARs are the binary form those entries write (uint32 len << 4 | op,
+ * d_cigar_len in bytes) and the extended CIGAR is written in the same form, = as 7 and X as 8, xcigar_len in bytes; otherwise both
+ * are text.  MD is text either way.
+ * d_status_in (optional): where d_status_in[p] != 0 nothing of alignment p is read, its record is all zero and d_status_out[p] =
+ * d_status_in[p].  Otherwise the alignment is checked before any base is read: 0 <= t_beg <= t_end <= t_len and likewise for q;
+ * 0 <= cigar_len <= cigar_stride (binary: a multiple of 4); every element M / I / D with 1 <= len; and the sums of what the elements
+ * spend, taken in 64 bits, equal to the two spans.  Anything else is MGL_SW_ERR_BAD_ARG in d_status_out (optional) and an all-zero
+ * record, and no access leaves the arrays whatever the slot holds.
+ * d_stats_out[p].md_len and .xcigar_len are the lengths NEEDED, also where d_md_out / d_xcigar_out is NULL (a sizing pass).  A text
+ * longer than its stride gives MGL_SW_ERR_CIGAR_OVERFLOW: the slot then holds the first md_stride / xcigar_stride bytes of it (whole
+ * words in the binary form) and the counts are still right.  Bytes at or beyond a text's length are not written.
+ * OVER-READ RULE: the sequences may be read in aligned words.  No byte is read outside the aligned 16-byte blocks that hold a byte of
+ * a span, so a span may start and end anywhere in memory the caller owns up to those borders.  (The present kernel reads single bytes
+ * and stays inside the spans.)
+ * MGL_SW_ERR_BAD_ARG before any device work for n < 0 or above 2^30, a null sequence / start / length / record / CIGAR / d_stats_out
+ * pointer, cigar_stride < 1, md_stride < 1 with d_md_out, xcigar_stride < 1 with d_xcigar_out, and with MGL_SW_FLAG_BINARY_CIGAR a
+ * cigar_stride or (with d_xcigar_out) xcigar_stride that is no multiple of 4; MGL_SW_ERR_DEVICE without a GPU.  n = 0 is MGL_SW_OK.
+ * Device work on `stream`, no synchronisation, no workspace: sw_describe_kernel, one wave per alignment.  No MGL_SW_KERNEL_* id: the
+ * timing record keeps its fill_kernel.
+ */
+typedef struct mgl_sw_alignment_stats {
+    int32_t n_match, n_mismatch, n_ins, n_del, n_ins_runs, n_del_runs, md_len, xcigar_len;
+} mgl_sw_alignment_stats;
+
+int mgl_sw_describe_alignments_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets, const int64_t *d_t_start,
+                                            const int32_t *d_t_len, const uint8_t *d_queries, const int64_t *d_q_start, const int32_t *d_q_len,
+                                            const mgl_sw_chain_alignment *d_aln, const char *d_cigar, int cigar_stride, const int32_t *d_cigar_len,
+                                            const int32_t *d_status_in, mgl_sw_alignment_stats *d_stats_out, char *d_md_out, int md_stride,
+                                            char *d_xcigar_out, int xcigar_stride, int32_t *d_status_out, int flags);
+
+/*
  * Logical backtrack matrix of one pair, the reference's calculateMatrix
  * (sw_scalar.h:7 / sw.cpp:5-146): btr is (tl+1)*(ql+1) int32 row-major with
  * row 0 / column 0 zero, +k = k rows up (deletion run), -k = k columns left

@@ -246,3 +246,96 @@ def bam_pairs(path, window=None, seed=7, min_mapq=0):
         qs.append(rec.seq)
         used.append(rec)
     return ts, qs, used
+
+
+# --------------------------------------------------------------------------------------------- SAM / PAF
+def sam_header(ref_name, ref_len):
+    """The header of a SAM file over one reference sequence."""
+    return "@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:%s\tLN:%d\n@PG\tID:mgl_amd\tPN:mgl_amd\n" % (ref_name, int(ref_len))
+
+
+def _oriented(seq, strand):
+    from . import synth
+
+    return synth.revcomp(seq) if strand else bytes(seq)
+
+
+def _mapped(result, k):
+    return int(result.status[k]) == 0 and int(result.ref_end[k]) > int(result.ref_beg[k])
+
+
+def _core_cigar(result, k, extended):
+    if extended:
+        if result.xcigars is None:
+            raise ValueError("the result has no extended CIGARs: map_reads_described(..., extended=True)")
+        return result.xcigars[k]
+    return result.cigars[k]
+
+
+def write_sam(path, ref_name, ref_len, names, reads, quals, result, extended=False):
+    """One SAM line per read from a DescribedMapResult (MicrosoftSmithWaterman.map_reads_described).  ``reads``: the reads as they
+    were given; ``quals``: their qualities as text (phred + 33), or None for ``*``.  A mapped read: FLAG 0 or 16, POS ref_beg + 1, the
+    result's MAPQ, CIGAR = q_beg S, the core (the = / X form with ``extended``), (read length - q_end) S, SEQ the ORIENTED read (its
+    reverse complement on strand 1, QUAL reversed with it), tags NM:i, MD:Z, AS:i.  An unmapped read: FLAG 4, ``*`` and 0, SEQ and
+    QUAL as given."""
+    with open(path, "wt") as f:
+        f.write(sam_header(ref_name, ref_len))
+        for k, (name, read) in enumerate(zip(names, reads)):
+            read = bytes(read)
+            qual = None if quals is None or quals[k] is None else (quals[k] if isinstance(quals[k], str) else bytes(quals[k]).decode())
+            if not _mapped(result, k):
+                f.write("\t".join([name, "4", "*", "0", "0", "*", "*", "0", "0", read.decode(), qual or "*"]) + "\n")
+                continue
+            strand, qb, qe = int(result.strand[k]), int(result.q_beg[k]), int(result.q_end[k])
+            cigar = ("%dS" % qb if qb else "") + _core_cigar(result, k, extended) + ("%dS" % (len(read) - qe) if len(read) > qe else "")
+            if qual is not None and strand:
+                qual = qual[::-1]
+            f.write("\t".join([name, "16" if strand else "0", ref_name, str(int(result.ref_beg[k]) + 1), str(int(result.mapq[k])), cigar, "*", "0", "0",
+                               _oriented(read, strand).decode(), qual or "*", "NM:i:%d" % int(result.nm[k]), "MD:Z:" + bytes(result.md[k]).decode("latin-1"),
+                               "AS:i:%d" % int(result.score[k])]) + "\n")
+
+
+def write_paf(path, ref_name, ref_len, names, reads, result, extended=False):
+    """One PAF line per MAPPED read from a DescribedMapResult: the twelve columns -- query name, length, start and end on the ORIGINAL
+    strand ([ql - q_end, ql - q_beg) for strand 1), strand, target name, length, start, end, matching bases, block length, MAPQ --
+    and the tags NM:i, AS:i and cg:Z: (the core CIGAR, without clips; the = / X form with ``extended``).  An unmapped read has no
+    line."""
+    with open(path, "wt") as f:
+        for k, (name, read) in enumerate(zip(names, reads)):
+            if not _mapped(result, k):
+                continue
+            ql, strand, qb, qe = len(read), int(result.strand[k]), int(result.q_beg[k]), int(result.q_end[k])
+            lo, hi = (ql - qe, ql - qb) if strand else (qb, qe)
+            f.write("\t".join([name, str(ql), str(lo), str(hi), "-" if strand else "+", ref_name, str(int(ref_len)), str(int(result.ref_beg[k])),
+                               str(int(result.ref_end[k])), str(int(result.n_match[k])), str(int(result.block_len[k])), str(int(result.mapq[k])),
+                               "NM:i:%d" % int(result.nm[k]), "AS:i:%d" % int(result.score[k]), "cg:Z:" + _core_cigar(result, k, extended)]) + "\n")
+
+
+def read_sam(path):
+    """A small SAM reader: (header text, [(reference name, length)], [BamRecord]) as ``read_bam`` gives them -- ``pos`` 0-based (-1
+    for ``*``), ``cigar`` a list of (len, op), ``seq`` ASCII bytes, ``qual`` raw phred bytes (empty for ``*``), ``tags`` with i / f
+    values converted -- so that ``reference_under_read`` works on the records."""
+    header, refs, records = [], [], []
+    with _open(path) as f:
+        for line in f:
+            line = line.rstrip("\r\n")
+            if not line:
+                continue
+            if line.startswith("@"):
+                header.append(line)
+                if line.startswith("@SQ"):
+                    kv = dict(x.split(":", 1) for x in line.split("\t")[1:])
+                    refs.append((kv["SN"], int(kv["LN"])))
+                continue
+            c = line.split("\t")
+            if len(c) < 11:
+                raise ValueError("malformed SAM line %r" % line[:40])
+            tags = {}
+            for t in c[11:]:
+                tag, ty, val = t.split(":", 2)
+                tags[tag] = int(val) if ty == "i" else float(val) if ty == "f" else val
+            names = [r[0] for r in refs]
+            records.append(BamRecord(c[0], names.index(c[2]) if c[2] in names else -1, int(c[3]) - 1, int(c[1]), int(c[4]),
+                                     [] if c[5] == "*" else cigar_text_to_elements(c[5]), b"" if c[9] == "*" else c[9].encode(),
+                                     b"" if c[10] == "*" else bytes(ord(x) - 33 for x in c[10]), tags))
+    return "\n".join(header) + ("\n" if header else ""), refs, records

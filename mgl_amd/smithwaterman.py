@@ -42,6 +42,9 @@ ChainAnchorsResult = namedtuple("ChainAnchorsResult", "chains score status")
 SeedResult = namedtuple("SeedResult", "candidates status")
 MapResult = namedtuple("MapResult", "ref_beg ref_end strand score cigars status")
 RankedMapResult = namedtuple("RankedMapResult", "ref_beg ref_end strand score cigars status mapq n_chains secondary")
+DescribedMapResult = namedtuple("DescribedMapResult", "ref_beg ref_end strand score cigars status mapq n_chains secondary q_beg q_end nm n_match block_len md "
+                                "xcigars")
+AlignmentStats = namedtuple("AlignmentStats", "n_match n_mismatch n_ins n_del n_ins_runs n_del_runs md_len xcigar_len")
 RankedChain = namedtuple("RankedChain", "score strand n_anchors t_beg t_end q_beg q_end parent n_sub subsc mapq end_index")
 IndexInfo = namedtuple("IndexInfo", "ref_len entries bytes k w")
 
@@ -914,6 +917,133 @@ class MicrosoftSmithWaterman:
         return RankedMapResult(np.where(ok, t_start + rec[:, 1], 0), np.where(ok, t_start + rec[:, 2], 0), np.where(ok, strand, 0).astype(np.int32),
                                np.where(ok, rec[:, 0], 0).astype(np.int32), CigarColumn(cg, ln), np.where(wst != 0, wst, st).astype(np.int32), mapq,
                                nc.astype(np.int32), secondary)
+
+    def describe_device(self, targets, t_start, t_len, queries, q_start, q_len, aln, cigar, cigar_stride, cigar_len, status_in=None, md_stride=None,
+                        xcigar_stride=None, binary_cigar=False, md=True, xcigar=True, out=None):
+        """mgl_sw_describe_alignments_batch_device on device tensors: the six sequence tensors, the records [n, 8], the CIGAR bytes
+        [n * cigar_stride] and their lengths as ``align_chain_device`` or ``extend_seed_device`` took and wrote them, and optionally
+        their status (an alignment with a non-zero one is not read); enqueued on the current stream, not synchronised.  Returns
+        (stats [n, 8] int32 -- mgl_sw_alignment_stats' fields --, md bytes [n * md_stride] or None, xcigar bytes [n * xcigar_stride]
+        or None, status [n]) tensors; without ``md`` / ``xcigar`` that text is not written and its length still is (a sizing pass).
+        The strides default to ``cigar_stride``; a text that does not fit is MGL_SW_ERR_CIGAR_OVERFLOW in the status.  ``out``: such
+        a tuple to write into (its status may be None), whose text tensors decide what is written."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(t_start.numel())
+        dev = targets.device
+        md_stride = int(cigar_stride if md_stride is None else md_stride)
+        xcigar_stride = int(cigar_stride if xcigar_stride is None else xcigar_stride)
+        if out is None:
+            u8 = lambda want, stride: torch.empty(n * max(stride, 0), dtype=torch.uint8, device=dev) if want else None  # noqa: E731
+            out = (torch.empty((n, 8), dtype=torch.int32, device=dev), u8(md, md_stride), u8(xcigar, xcigar_stride), torch.empty(n, dtype=torch.int32, device=dev))
+        stats, mdt, xct, st = out
+        assert stats.numel() >= 8 * n and (mdt is None or mdt.numel() >= n * md_stride) and (xct is None or xct.numel() >= n * xcigar_stride)
+        spare = torch.empty(2, dtype=torch.int64, device=dev)  # an empty tensor has no address: the entry wants one
+        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        rc = _lib.lib().mgl_sw_describe_alignments_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len), ptr(aln),
+            ptr(cigar), int(cigar_stride), ptr(cigar_len), ptr(status_in), ptr(stats), ptr(mdt), md_stride, ptr(xct), xcigar_stride, ptr(st),
+            _lib.FLAG_BINARY_CIGAR if binary_cigar else 0)
+        _check(rc, ctx)
+        return out
+
+    def describe(self, refs, alts, cigars, spans=None, binary_cigar=False, return_status=False):
+        """mgl_sw_describe_alignments_batch_device over lists: ``cigars[k]`` (text, M / I / D) lays ``refs[k][t_beg:t_end]`` against
+        ``alts[k][q_beg:q_end]``, ``spans[k]`` = (t_beg, t_end, q_beg, q_end), by default the whole of both (tests/describe_textbook.py).
+        NOT a reference function.  A sizing pass finds the longest texts, a second call writes them.  Returns ([AlignmentStats], [md
+        bytes], [extended CIGAR text]); with ``binary_cigar`` the CIGARs travel in the BAM encoding both ways (the result is text all
+        the same); with ``return_status`` also the status array, and no exception for an alignment's status."""
+        import torch
+
+        from . import formats
+
+        dev = torch.device("cuda", self._device)
+        n, packed, _ = _pack_pairs(refs, alts, dev, 16, False)
+        assert len(cigars) == n
+        if binary_cigar:
+            rows = [formats.cigar_elements_to_binary(formats.cigar_text_to_elements(c)).astype("<u4").tobytes() for c in cigars]
+        else:
+            rows = [c.encode() if isinstance(c, str) else bytes(c) for c in cigars]
+        stride = (max([len(r) for r in rows] + [4]) + 3) // 4 * 4
+        slots = np.zeros((n, stride), np.uint8)
+        for k, r in enumerate(rows):
+            slots[k, :len(r)] = np.frombuffer(r, np.uint8)
+        if spans is None:
+            spans = [(0, len(t), 0, len(q)) for t, q in zip(refs, alts)]
+        rec = np.zeros((n, 8), np.int32)
+        rec[:, 1:5] = np.asarray(spans, np.int32).reshape(n, 4)
+        g = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+        args = (*packed[:6], g(rec), g(slots.reshape(-1)), stride, g(np.asarray([len(r) for r in rows], np.int32)))
+        sized = self.describe_device(*args, binary_cigar=binary_cigar, md=False, xcigar=False)
+        need = _fetch(sized, dev, True)[0].reshape(n, 8)
+        ms, xs = max(int(need[:, 6].max(initial=1)), 1), (max(int(need[:, 7].max(initial=4)), 4) + 3) // 4 * 4
+        stats, md, xc, st = _fetch(self.describe_device(*args, md_stride=ms, xcigar_stride=xs, binary_cigar=binary_cigar), dev, return_status)
+        stats, md, xc = stats.reshape(n, 8), md.reshape(n, ms), xc.reshape(n, xs)
+        mds = [md[k, :stats[k, 6]].tobytes() for k in range(n)]
+        if binary_cigar:
+            xcs = [formats.cigar_binary_to_text(np.frombuffer(xc[k, :stats[k, 7]].tobytes(), "<u4")) for k in range(n)]
+        else:
+            xcs = [xc[k, :stats[k, 7]].tobytes().decode() for k in range(n)]
+        res = ([AlignmentStats(*(int(v) for v in row)) for row in stats], mds, xcs)
+        return res + (st,) if return_status else res
+
+    def map_reads_described_device(self, index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters=GATK_PARAMETERS, md_stride=None,
+                                   xcigar_stride=None, xcigar=True, describe_out=None, **stages):
+        """``map_reads_ranked_device`` and ``describe_device`` behind it on the index's reference, the read's window, the oriented
+        reads and the alignment's own tensors, on the current stream, nothing read back and nothing synchronised in between.  A read
+        the alignment refused (unmapped ones among them) keeps that status and has an all-zero record.  ``stages``: the further
+        arguments of ``map_reads_ranked_device``.  Returns its six tuples and ``describe_device``'s:
+        (seeds, chain, chosen, window, aln, ranked, described)."""
+        binary = bool(stages.get("binary_cigar", False))
+        if stages.get("cigar_stride") is None:
+            stages["cigar_stride"] = _default_stride(max_tl, max_ql, binary)
+        stride = int(stages["cigar_stride"])
+        seeds, chain, chosen, window, aln, ranked = self.map_reads_ranked_device(index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters, **stages)
+        oriented = chosen[1] if chosen is not None else queries
+        described = self.describe_device(index.ref, window[0], window[1], oriented, q_start, q_len, aln[0], aln[4], stride, aln[5], aln[6], md_stride,
+                                         xcigar_stride, binary, xcigar=xcigar, out=describe_out)
+        return seeds, chain, chosen, window, aln, ranked, described
+
+    def map_reads_described(self, index, reads, band=64, zdrop=-1, parameters=GATK_PARAMETERS, slack=200, strands=2, max_tl=None, extended=False, **stages):
+        """``map_reads_described_device`` over a list of byte strings: ``map_reads_ranked`` with what a SAM or PAF record needs
+        (``formats.write_sam`` / ``write_paf`` take the result as it is).  Returns DescribedMapResult: RankedMapResult's fields as
+        ``map_reads_ranked`` gives them, and per read ``q_beg`` / ``q_end`` (the aligned part of the ORIENTED read; what lies outside
+        is a soft clip), ``nm`` (mismatches + inserted + deleted bases), ``n_match``, ``block_len`` (n_match + nm), ``md`` (a list of
+        bytes) and, with ``extended``, ``xcigars`` (the = / X CIGARs; None otherwise).  An unmapped or refused read has zeros, an
+        empty MD and an empty extended CIGAR."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        qs = [bytes(q) for q in reads]
+        n, packed, _ = _pack_pairs(qs, qs, dev, 16, False)
+        max_ql = packed[7]
+        if max_tl is None:
+            max_tl = max_ql + max_ql // 2 + 2 * int(slack)
+        stride = stages.pop("cigar_stride", None) or _default_stride(max_tl, max_ql, False)
+        _, _, chosen, window, aln, ranked, desc = self.map_reads_described_device(index, *packed[3:6], max_tl, max_ql, band, zdrop, parameters, strands=strands,
+                                                                                  slack=slack, cigar_stride=stride, xcigar=bool(extended), **stages)
+        torch.cuda.synchronize(dev)
+        rec, cg, ln, st = aln[0].cpu().numpy(), aln[4].cpu().numpy().reshape(n, stride), aln[5].cpu().numpy(), aln[6].cpu().numpy()
+        t_start, wst = window[0].cpu().numpy(), window[3].cpu().numpy()
+        ok = st == 0
+        strand = chosen[0].cpu().numpy() if chosen is not None else np.zeros(n, np.int32)
+        ln = np.where(ok, ln, 0).astype(np.int32)
+        nc, rr = ranked[0].cpu().numpy(), ranked[1].cpu().numpy()
+        mapq = np.asarray([int(rr[p, 0, 10]) if nc[p] > 0 else 0 for p in range(n)], dtype=np.int32)
+        secondary = [[(int(c[3]), int(c[4]), int(c[1]), int(c[0]), int(c[7])) for c in rr[p, 1:nc[p]]] for p in range(n)]
+        stats, dst = desc[0].cpu().numpy().reshape(n, 8), desc[3].cpu().numpy()
+        over = np.flatnonzero(ok & (dst != 0))
+        if over.size:  # the alignment stands and its description does not: a text beyond its stride
+            raise _lib.MglSwError(int(dst[over[0]]), f"describing read {int(over[0])}")
+        md = desc[1].cpu().numpy().reshape(n, -1)
+        mds = [md[p, :stats[p, 6]].tobytes() for p in range(n)]
+        nm = (stats[:, 1] + stats[:, 2] + stats[:, 3]).astype(np.int32)
+        z = lambda x: np.where(ok, x, 0).astype(np.int32)  # noqa: E731
+        return DescribedMapResult(np.where(ok, t_start + rec[:, 1], 0), np.where(ok, t_start + rec[:, 2], 0), z(strand), z(rec[:, 0]), CigarColumn(cg, ln),
+                                  np.where(wst != 0, wst, st).astype(np.int32), mapq, nc.astype(np.int32), secondary, z(rec[:, 3]), z(rec[:, 4]), nm,
+                                  stats[:, 0].astype(np.int32), (stats[:, 0] + nm).astype(np.int32),
+                                  mds, CigarColumn(desc[2].cpu().numpy().reshape(n, -1), stats[:, 7].astype(np.int32)) if extended else None)
 
     def align_packed_2bit(self, target_bases, target_base_count, t_start, t_len, query_bases, query_base_count, q_start, q_len,
                           max_tl, max_ql, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,
