@@ -1,14 +1,11 @@
 // sw_banded.cpp -- mgl_sw_align_batch_device_banded (include/mgl_sw.h): the GATK function over a diagonal band.  Host side only: argument
-// checks, the workspace slots and the launch of sw_banded_kernel (sw_banded.hip).  Its own translation unit: the context is reached
-// through the accessors at the end of sw_capi.cpp (sw_ctx_access.h), so the host-sanitizer build of sw_capi.cpp (tests/cpp) needs nothing of the kernel.
+// checks and the launch of sw_banded_kernel (sw_banded.hip) on workspace slots (sw_band_host.h).  The entry's frame is sw_stage_host.h's.
 #include "../../include/mgl_sw.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
-#include <string>
 
 #include "sw_band_host.h"
 
@@ -35,18 +32,11 @@ int mgl_sw_align_batch_device_banded(mgl_sw_ctx *ctx, void *stream, int64_t n, c
     else if (max_tl < 1 || max_ql < 1) bad = "max_tl / max_ql < 1";
     else if (score_only && !d_score_out) bad = "MGL_SW_FLAG_SCORE_ONLY without a score array";
     else if (!score_only && (!d_cigar_out || !d_cigar_len_out || cigar_stride < (binary ? 4 : 2))) bad = "CIGAR array missing or cigar_stride too small";
-    if (bad) {
-        if (ctx) {
-            std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-            ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, (std::string("mgl_sw_align_batch_device_banded: ") + bad).c_str());
-        }
-        return MGL_SW_ERR_BAD_ARG;
-    }
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
+    if (bad) return refuse(ctx, "mgl_sw_align_batch_device_banded", bad);
+    if (!ctx) return no_context();
+    Stage stage(ctx, stream);
     if (n == 0) return MGL_SW_OK;
     mgl_sw_normalize_params(&match, &mismatch, &gopen, &gext);
-    hipStream_t st = static_cast<hipStream_t>(stream);
 
     BandedArgs a{};
     a.t = SeqSet{d_targets, d_t_start, d_t_len, max_tl, 0};
@@ -69,7 +59,7 @@ int mgl_sw_align_batch_device_banded(mgl_sw_ctx *ctx, void *stream, int64_t n, c
     a.binary_cigar = binary ? 1 : 0;
     a.score_only = score_only ? 1 : 0;
     // ---- the slots are sized for the largest pair the bounds admit
-    return launch_on_slots(ctx, st, a, banded_slot_bound(std::min(max_tl, BANDED_MAX_LEN), std::min(max_ql, BANDED_MAX_LEN), a.band, score_only), launch_banded,
+    return launch_on_slots(stage, a, banded_slot_bound(std::min(max_tl, BANDED_MAX_LEN), std::min(max_ql, BANDED_MAX_LEN), a.band, score_only), launch_banded,
                            "launch_banded", MGL_SW_KERNEL_BANDED);
 }
 

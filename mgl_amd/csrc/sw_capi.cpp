@@ -1532,12 +1532,14 @@ MGL_SW_INTERNAL int ctx_borrow_workspace(mgl_sw_ctx *ctx, hipStream_t st, size_t
 }
 
 // the call's last kernel is enqueued on `stream`: the next call waits for it before it touches the workspace.  The timing record
-// (mgl_sw_ctx_get_timing) names the kernel and its launches (no events: the call is not profiled)
+// (mgl_sw_ctx_get_timing) names the kernel and its launches (no events: the call is not profiled); kKeepFillKernel, for a stage
+// without a kernel id: the record keeps the fill_kernel it has, read here, under the caller's lock, before the record is reset
 MGL_SW_INTERNAL int ctx_return_workspace(mgl_sw_ctx *ctx, hipStream_t st, int fill_kernel, int launches)
 {
     HIP_TRY(ctx, hipEventRecord(ctx->ws_idle, st));
     ctx->ws_idle_set = true;
     ctx->last_chunk_count = 0; // (no slot of this call can be expanded)
+    if (fill_kernel == kKeepFillKernel) fill_kernel = ctx->timing.fill_kernel;
     if (ctx->profiling != 3) {
         ctx->timing = mgl_sw_timing{};
         ctx->pool_used = 0;

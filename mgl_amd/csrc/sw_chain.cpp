@@ -2,15 +2,14 @@
 // of it joined into one alignment.  Host side only: argument checks, one workspace for the staging of the whole
 // batch and the slots, and five launches on the caller's stream -- sw_chain_split_kernel, the extension kernel over the left flanks and
 // over the right ones (sw_extend.hip or sw_extend_adaptive.hip, as they are), sw_gap_fill_kernel, sw_chain_join_kernel -- behind two
-// memsets (the gap descriptors, d_gap_score_out).  No synchronisation.  Its own translation unit, like sw_seed_extend.cpp.
+// memsets (the gap descriptors, d_gap_score_out).  No synchronisation.  The entry's frame is sw_stage_host.h's, the two sides'
+// extension sw_band_host.h's.
 #include "../../include/mgl_sw.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
-#include <string>
 
 #include "sw_band_host.h"
 #include "sw_chain.h"
@@ -32,7 +31,6 @@ int mgl_sw_align_chain_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
                                     int32_t *d_cigar_len_out, int32_t *d_status_out, int flags)
 {
     const bool score_only = (flags & MGL_SW_FLAG_SCORE_ONLY) != 0, binary = (flags & MGL_SW_FLAG_BINARY_CIGAR) != 0;
-    const bool adaptive = (flags & MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND) != 0;
     // ---- arguments first: nothing below touches a device before they are known good
     const char *bad = nullptr;
     if (n < 0) bad = "n < 0";
@@ -45,36 +43,18 @@ int mgl_sw_align_chain_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
     else if (max_tl < 1 || max_ql < 1) bad = "max_tl / max_ql < 1";
     else if (max_gap_tl < 0 || max_gap_ql < 0) bad = "max_gap_tl / max_gap_ql < 0";
     else if (!score_only && (!d_cigar_out || !d_cigar_len_out || cigar_stride < (binary ? 4 : 2))) bad = "CIGAR array missing or cigar_stride too small";
-    if (bad) {
-        if (ctx) {
-            std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-            ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, (std::string("mgl_sw_align_chain_batch_device: ") + bad).c_str());
-        }
-        return MGL_SW_ERR_BAD_ARG;
-    }
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
+    if (bad) return refuse(ctx, "mgl_sw_align_chain_batch_device", bad);
+    if (!ctx) return no_context();
+    Stage stage(ctx, stream);
     if (n == 0) return MGL_SW_OK;
     mgl_sw_normalize_params(&match, &mismatch, &gopen, &gext);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipStream_t st = stage.st;
     // a gap bound of 0: no gap with bases on both sides is admitted, and a slot for a 1 x 1 gap is what stands there
     const int gap_tl = std::min(std::max(max_gap_tl, 1), BANDED_MAX_LEN), gap_ql = std::min(std::max(max_gap_ql, 1), BANDED_MAX_LEN);
 
-    // ---- the extension of one side: sw_seed_extend.cpp's
+    // ---- the extension of one side (sw_band_host.h)
     ExtendArgs e{};
-    e.match = match;
-    e.mismatch = mismatch;
-    e.gopen = gopen;
-    e.gext = gext;
-    e.band = adaptive ? (int)std::min<int64_t>({(int64_t)band, (int64_t)max_tl + max_ql, 2 * (int64_t)BANDED_MAX_LEN}) : clamp_band(band, max_tl, max_ql);
-    e.zdrop = zdrop;
-    e.max_tl = max_tl;
-    e.max_ql = max_ql;
-    e.binary_cigar = 1; // the internal rows: the join reads elements, not text
-    e.score_only = score_only ? 1 : 0;
-    e.to_query_end = (flags & MGL_SW_FLAG_EXTEND_TO_QUERY_END) ? 1 : 0;
-    const int cap_tl = std::min(max_tl, BANDED_MAX_LEN), cap_ql = std::min(max_ql, BANDED_MAX_LEN);
-    const int64_t ext_bound = adaptive ? extend_adaptive_pair_bytes(cap_tl, cap_ql, e.band, score_only) : extend_pair_bytes(cap_tl, cap_ql, e.band, score_only);
+    const int64_t ext_bound = extend_sides_setup(stage, e, match, mismatch, gopen, gext, flags, band, zdrop, max_tl, max_ql);
     // ---- the fill of a gap: the banded entry's band clamp and slot bound (sw_banded.cpp), at the gap bounds
     const int fill_band = clamp_band(band, gap_tl, gap_ql);
     const int64_t fill_bound = banded_slot_bound(gap_tl, gap_ql, fill_band, score_only);
@@ -82,7 +62,7 @@ int mgl_sw_align_chain_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
     // ---- one workspace: the staging of the whole batch, then the slots.  The extension launches and the fill follow one another on
     // the stream, so their slots share one region: each kind is cut from it at its own size, and a kind whose bound the region does
     // not hold gets one slot of all there is (a segment that does not fit its slot: MGL_SW_ERR_UNSUPPORTED)
-    const int64_t limit = std::max<int64_t>(ctx_workspace_limit(ctx), 256) / 256 * 256;
+    const int64_t limit = stage.limit();
     const ChainStaging sg = chain_staging(n, total_anchors, max_tl, max_ql, gap_tl, gap_ql, cigar_stride, binary, score_only);
     const int64_t room = limit - sg.bytes;
     if (room < 256)
@@ -91,10 +71,9 @@ int mgl_sw_align_chain_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
     const int64_t most = (int64_t)ctx_cus(ctx) * BANDED_WAVES_PER_CU;
     const int64_t ext_waves = std::max<int64_t>(1, std::min<int64_t>({n, most, room / ext_slot}));
     const int64_t fill_waves = std::max<int64_t>(1, std::min<int64_t>({std::max<int64_t>(total_anchors, 1), most, room / fill_slot}));
-    void *wsv = nullptr;
-    const int rc = ctx_borrow_workspace(ctx, st, (size_t)(sg.bytes + std::max(ext_waves * ext_slot, fill_waves * fill_slot)), &wsv);
+    unsigned char *ws = nullptr;
+    const int rc = stage.borrow((size_t)(sg.bytes + std::max(ext_waves * ext_slot, fill_waves * fill_slot)), &ws);
     if (rc != MGL_SW_OK) return rc;
-    unsigned char *const ws = static_cast<unsigned char *>(wsv);
     e.ws = ws + sg.bytes;
     e.slot_bytes = ext_slot;
     e.slots = (int)ext_waves;
@@ -123,23 +102,8 @@ int mgl_sw_align_chain_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
     s.gopen = gopen;
     s.gext = gext;
     s.band = fill_band;
-    s.rev_t = ws + sg.pair.rev_t;
-    s.rev_q = ws + sg.pair.rev_q;
-    s.tstride = sg.pair.tstride;
-    s.qstride = sg.pair.qstride;
-    for (int x = 0; x < 4; ++x) {
-        s.off[x] = reinterpret_cast<int64_t *>(ws + sg.pair.off[x]);
-        s.len[x] = reinterpret_cast<int32_t *>(ws + sg.pair.len[x]);
-    }
-    s.flank = reinterpret_cast<int4 *>(ws + sg.pair.flank);
+    bind_seed_staging(s, ws, sg.pair, score_only);
     s.pstat = reinterpret_cast<int32_t *>(ws + sg.pstat);
-    for (int x = 0; x < 2; ++x) {
-        s.side_ext[x] = reinterpret_cast<const Extension *>(ws + sg.pair.ext[x]);
-        s.side_status[x] = reinterpret_cast<const int32_t *>(ws + sg.pair.status[x]);
-        s.side_clen[x] = reinterpret_cast<const int32_t *>(ws + sg.pair.clen[x]);
-        s.side_cigar[x] = score_only ? nullptr : reinterpret_cast<const uint32_t *>(ws + sg.pair.cigar[x]);
-    }
-    s.istride = sg.pair.istride;
     s.owner = reinterpret_cast<int32_t *>(ws + sg.owner);
     s.gscore = reinterpret_cast<int32_t *>(ws + sg.gscore);
     s.gstatus = reinterpret_cast<int32_t *>(ws + sg.gstatus);
@@ -160,39 +124,21 @@ int mgl_sw_align_chain_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
     s.binary_cigar = binary ? 1 : 0;
     s.score_only = score_only ? 1 : 0;
 
-    auto launch_side = adaptive ? launch_extend_adaptive : launch_extend;
-    const int fill = adaptive ? MGL_SW_KERNEL_EXTEND_ADAPTIVE : MGL_SW_KERNEL_EXTEND;
-    int launches = 0;
-    // a step that fails behind others of this call: those still use the workspace, so it is returned (the next call on another
-    // stream waits for them) before the error is
-    auto give_up = [&](hipError_t he, const char *where) {
-        ctx_return_workspace(ctx, st, fill, launches);
-        return ctx_hip_fail(ctx, he, where);
-    };
     hipError_t he = hipSuccess;
     if (total_anchors > 0) he = hipMemsetAsync(s.owner, CHAIN_NO_OWNER & 0xff, (size_t)total_anchors * 4, st); // every anchor unclaimed
-    if (he != hipSuccess) return give_up(he, "hipMemsetAsync(gap descriptors)");
+    if (he != hipSuccess) return stage.fail(he, "hipMemsetAsync(gap descriptors)");
     if (d_gap_score_out && total_anchors > 0) he = hipMemsetAsync(d_gap_score_out, 0, (size_t)total_anchors * 4, st);
-    if (he != hipSuccess) return give_up(he, "hipMemsetAsync(d_gap_score_out)");
+    if (he != hipSuccess) return stage.fail(he, "hipMemsetAsync(d_gap_score_out)");
     he = launch_chain_split(s, st);
-    if (he != hipSuccess) return give_up(he, "launch_chain_split");
-    for (int side = 0; side < 2; ++side) { // 0: the reversed copies of the left flanks; 1: the right flanks in the caller's arrays
-        e.t = SeqSet{side ? d_targets : s.rev_t, s.off[2 * side], s.len[2 * side], max_tl, 0};
-        e.q = SeqSet{side ? d_queries : s.rev_q, s.off[2 * side + 1], s.len[2 * side + 1], max_ql, 0};
-        e.ext = reinterpret_cast<Extension *>(ws + sg.pair.ext[side]);
-        e.status = reinterpret_cast<int32_t *>(ws + sg.pair.status[side]);
-        e.cigar = score_only ? nullptr : reinterpret_cast<char *>(ws + sg.pair.cigar[side]);
-        e.cigar_len = reinterpret_cast<int32_t *>(ws + sg.pair.clen[side]);
-        he = launch_side(e, st);
-        if (he != hipSuccess) return give_up(he, adaptive ? "launch_extend_adaptive" : "launch_extend");
-        ++launches;
-    }
+    if (he != hipSuccess) return stage.fail(he, "launch_chain_split");
+    const int src = launch_extend_sides(stage, e, s, ws, sg.pair);
+    if (src != MGL_SW_OK) return src;
     he = launch_gap_fill(s, st);
-    if (he != hipSuccess) return give_up(he, "launch_gap_fill");
-    ++launches;
+    if (he != hipSuccess) return stage.fail(he, "launch_gap_fill");
+    ++stage.launches;
     he = launch_chain_join(s, st);
-    if (he != hipSuccess) return give_up(he, "launch_chain_join");
-    return ctx_return_workspace(ctx, st, fill, launches);
+    if (he != hipSuccess) return stage.fail(he, "launch_chain_join");
+    return stage.done();
 }
 
 } // extern "C"

@@ -1,19 +1,17 @@
 // sw_chain_dp.cpp -- mgl_sw_chain_anchors_batch_device (include/mgl_sw.h): candidate anchors in, the best colinear chain of every read
 // out, in the CSR layout mgl_sw_align_chain_batch_device reads.  Host side only: argument checks, one workspace
 // (the counts, the staging of the chains, and pred slots where max_cand is above what a wave keeps in LDS) and three launches on the
-// caller's stream -- sw_chain_dp_kernel, sw_chain_dp_scan_kernel, sw_chain_dp_pack_kernel.  No synchronisation.  Its own translation
-// unit, like sw_chain.cpp.
+// caller's stream -- sw_chain_dp_kernel, sw_chain_dp_scan_kernel, sw_chain_dp_pack_kernel.  No synchronisation.  The entry's frame is
+// sw_stage_host.h's.
 #include "../../include/mgl_sw.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
-#include <string>
 
 #include "sw_chain_dp.h"
-#include "sw_ctx_access.h"
+#include "sw_stage_host.h"
 
 using namespace mgl_sw_dev;
 using namespace mgl_sw_host;
@@ -38,34 +36,24 @@ int mgl_sw_chain_anchors_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
     else if (max_dist_t < 0 || max_dist_q < 0 || bw < 0) bad = "max_dist_t, max_dist_q or bw < 0";
     else if (pen_gap < 0 || pen_skip < 0) bad = "pen_gap or pen_skip < 0";
     else if (!chain_dp_pen_ok(max_dist_t, max_dist_q, bw, pen_gap, pen_skip)) bad = "pen_gap * bw + pen_skip * min(max_dist_t, max_dist_q) >= 2^31";
-    if (bad) {
-        if (ctx) {
-            std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-            ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, (std::string("mgl_sw_chain_anchors_batch_device: ") + bad).c_str());
-        }
-        return MGL_SW_ERR_BAD_ARG;
-    }
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
-    // there is no kernel id for this stage: the timing record keeps the fill_kernel it has (read before the context is locked)
-    mgl_sw_timing before{};
-    const int trc = mgl_sw_ctx_get_timing(ctx, &before);
-    if (trc != MGL_SW_OK) return trc;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (bad) return refuse(ctx, "mgl_sw_chain_anchors_batch_device", bad);
+    if (!ctx) return no_context();
+    // there is no kernel id for this stage: the timing record keeps the fill_kernel it has (Stage's default)
+    Stage stage(ctx, stream);
+    hipStream_t st = stage.st;
     max_cand = (int)std::min<int64_t>(max_cand, total_cand); // (no read that passes the range check has more)
 
     // ---- one workspace: the counts and the staging of the whole batch, then one pred slot per wave where LDS does not hold pred
-    const int64_t limit = std::max<int64_t>(ctx_workspace_limit(ctx), 256) / 256 * 256;
+    const int64_t limit = stage.limit();
     const ChainDpStaging sg = chain_dp_staging(n, total_cand, max_cand);
     const int64_t room = limit - sg.bytes;
     if (room < std::max<int64_t>(sg.slot_bytes, 0) || room < 0)
         return ctx_fail(ctx, MGL_SW_ERR_NOMEM, "mgl_sw_chain_anchors_batch_device: the workspace limit does not hold the batch's staging beside a pred slot: split the batch");
     int64_t waves = std::min<int64_t>(std::max<int64_t>(n, 1), (int64_t)ctx_cus(ctx) * CHAIN_DP_WAVES_PER_CU);
     if (sg.slot_bytes > 0) waves = std::min(waves, room / sg.slot_bytes);
-    void *wsv = nullptr;
-    const int rc = ctx_borrow_workspace(ctx, st, (size_t)(sg.bytes + waves * sg.slot_bytes), &wsv);
+    unsigned char *ws = nullptr;
+    const int rc = stage.borrow((size_t)(sg.bytes + waves * sg.slot_bytes), &ws);
     if (rc != MGL_SW_OK) return rc;
-    unsigned char *const ws = static_cast<unsigned char *>(wsv);
 
     ChainDpArgs a{};
     a.t_len = d_t_len;
@@ -98,18 +86,13 @@ int mgl_sw_chain_anchors_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
     a.pred_out = d_pred_out;
     a.status = d_status_out;
 
-    // a step that fails behind others of this call: those still use the workspace, so it is returned before the error is
-    auto give_up = [&](hipError_t he, const char *where) {
-        ctx_return_workspace(ctx, st, before.fill_kernel, 0);
-        return ctx_hip_fail(ctx, he, where);
-    };
     hipError_t he = launch_chain_dp(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_chain_dp");
+    if (he != hipSuccess) return stage.fail(he, "launch_chain_dp");
     he = launch_chain_dp_scan(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_chain_dp_scan");
+    if (he != hipSuccess) return stage.fail(he, "launch_chain_dp_scan");
     he = launch_chain_dp_pack(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_chain_dp_pack");
-    return ctx_return_workspace(ctx, st, before.fill_kernel, 0);
+    if (he != hipSuccess) return stage.fail(he, "launch_chain_dp_pack");
+    return stage.done();
 }
 
 } // extern "C"

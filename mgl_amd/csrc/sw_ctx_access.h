@@ -2,6 +2,7 @@
 // of a context: the accessors defined at the end of sw_capi.cpp, declared here once.  C++ names, hidden.  The caller holds
 // ctx_mutex(ctx) around every other one.  sw_capi.cpp includes this too, so that the compiler checks each definition against its
 // declaration; no kernel header is included here, so the host-sanitizer build of sw_capi.cpp (tests/cpp) needs nothing of the kernels.
+// The frame of a stage entry on top of these -- the lock, the workspace, the way out -- is sw_stage_host.h.
 #ifndef MGL_SW_CTX_ACCESS_H
 #define MGL_SW_CTX_ACCESS_H
 
@@ -17,6 +18,9 @@
 #define MGL_SW_INTERNAL __attribute__((visibility("hidden")))
 
 namespace mgl_sw_host {
+// ctx_return_workspace's fill_kernel for a stage that has no MGL_SW_KERNEL_* id: the timing record keeps the one it has
+constexpr int kKeepFillKernel = -1;
+
 MGL_SW_INTERNAL std::mutex &ctx_mutex(mgl_sw_ctx *ctx);
 MGL_SW_INTERNAL int ctx_device(mgl_sw_ctx *ctx);
 MGL_SW_INTERNAL int ctx_cus(mgl_sw_ctx *ctx);

@@ -1,7 +1,7 @@
 // sw_describe.cpp -- mgl_sw_describe_alignments_batch_device (include/mgl_sw.h): an alignment entry's records and CIGAR slots in, the
 // counts, the MD text and the extended CIGAR of every alignment out.  Host side only: argument checks and one
 // launch on the caller's stream, sw_describe_kernel.  No workspace and no synchronisation; the timing record is not touched, so it
-// keeps the fill_kernel it has.  Its own translation unit, like sw_rank.cpp.
+// keeps the fill_kernel it has.  The entry's frame is sw_stage_host.h's.
 #include "../../include/mgl_sw.h"
 
 #include <hip/hip_runtime.h>
@@ -9,11 +9,9 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
-#include <mutex>
-#include <string>
 
-#include "sw_ctx_access.h"
 #include "sw_describe.h"
+#include "sw_stage_host.h"
 
 using namespace mgl_sw_dev;
 using namespace mgl_sw_host;
@@ -46,17 +44,10 @@ int mgl_sw_describe_alignments_batch_device(mgl_sw_ctx *ctx, void *stream, int64
     else if (cigar_stride < 1 || (binary && cigar_stride % 4 != 0)) bad = "cigar_stride below 1, or no multiple of 4 for binary CIGARs";
     else if (d_md_out && md_stride < 1) bad = "md_stride below 1";
     else if (d_xcigar_out && (xcigar_stride < 1 || (binary && xcigar_stride % 4 != 0))) bad = "xcigar_stride below 1, or no multiple of 4 for binary CIGARs";
-    if (bad) {
-        if (ctx) {
-            std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-            ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, (std::string("mgl_sw_describe_alignments_batch_device: ") + bad).c_str());
-        }
-        return MGL_SW_ERR_BAD_ARG;
-    }
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
+    if (bad) return refuse(ctx, "mgl_sw_describe_alignments_batch_device", bad);
+    if (!ctx) return no_context();
     if (n == 0) return MGL_SW_OK;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    Stage stage(ctx, stream);
 
     DescribeArgs a{};
     a.targets = d_targets;
@@ -80,9 +71,9 @@ int mgl_sw_describe_alignments_batch_device(mgl_sw_ctx *ctx, void *stream, int64
     a.md = d_md_out;
     a.xcigar = d_xcigar_out;
     a.status = d_status_out;
-    const hipError_t he = launch_describe(a, st);
-    if (he != hipSuccess) return ctx_hip_fail(ctx, he, "launch_describe");
-    return MGL_SW_OK;
+    const hipError_t he = launch_describe(a, stage.st);
+    if (he != hipSuccess) return stage.fail(he, "launch_describe");
+    return stage.done(); // (no workspace: the timing record is not touched)
 }
 
 } // extern "C"

@@ -1,16 +1,13 @@
 // sw_extend.cpp -- mgl_sw_extend_batch_device (include/mgl_sw.h): anchored extension with Z-drop over a band centred on the main
 // diagonal, or -- MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND -- re-centred every 64 rows.  Host side only: argument checks, the workspace slots and
-// the launch of sw_extend_kernel (sw_extend.hip) or sw_extend_adaptive_kernel (sw_extend_adaptive.hip).  Its own
-// translation unit, like sw_banded.cpp: the context is reached through the accessors at the end of sw_capi.cpp (sw_ctx_access.h), so the host-sanitizer
-// build of sw_capi.cpp (tests/cpp) needs nothing of the kernel.
+// the launch of sw_extend_kernel (sw_extend.hip) or sw_extend_adaptive_kernel (sw_extend_adaptive.hip), as sw_band_host.h has them.
+// The entry's frame is sw_stage_host.h's.
 #include "../../include/mgl_sw.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
-#include <string>
 
 #include "sw_band_host.h"
 #include "sw_extend.h"
@@ -39,18 +36,11 @@ int mgl_sw_extend_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const u
     else if (band < 0) bad = "band < 0";
     else if (max_tl < 1 || max_ql < 1) bad = "max_tl / max_ql < 1";
     else if (!score_only && (!d_cigar_out || !d_cigar_len_out || cigar_stride < (binary ? 4 : 2))) bad = "CIGAR array missing or cigar_stride too small";
-    if (bad) {
-        if (ctx) {
-            std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-            ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, (std::string("mgl_sw_extend_batch_device: ") + bad).c_str());
-        }
-        return MGL_SW_ERR_BAD_ARG;
-    }
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
+    if (bad) return refuse(ctx, "mgl_sw_extend_batch_device", bad);
+    if (!ctx) return no_context();
+    Stage stage(ctx, stream);
     if (n == 0) return MGL_SW_OK;
     mgl_sw_normalize_params(&match, &mismatch, &gopen, &gext);
-    hipStream_t st = static_cast<hipStream_t>(stream);
 
     ExtendArgs a{};
     a.t = SeqSet{d_targets, d_t_start, d_t_len, max_tl, 0};
@@ -60,9 +50,7 @@ int mgl_sw_extend_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const u
     a.mismatch = mismatch;
     a.gopen = gopen;
     a.gext = gext;
-    // a fixed band of max(tl, ql) covers a pair's matrix; one that follows the path does so wherever it stands only from tl + ql on, so
-    // the clamp that keeps the geometry in int32 (|d_k| <= max(tl, ql) <= BANDED_MAX_LEN, see sw_extend_adaptive.hip) is wider there
-    a.band = adaptive ? (int)std::min<int64_t>({(int64_t)band, (int64_t)max_tl + max_ql, 2 * (int64_t)BANDED_MAX_LEN}) : clamp_band(band, max_tl, max_ql);
+    a.band = clamp_extend_band(adaptive, band, max_tl, max_ql);
     a.zdrop = zdrop;
     a.max_tl = max_tl;
     a.max_ql = max_ql;
@@ -74,13 +62,10 @@ int mgl_sw_extend_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const u
     a.binary_cigar = binary ? 1 : 0;
     a.score_only = score_only ? 1 : 0;
     a.to_query_end = (flags & MGL_SW_FLAG_EXTEND_TO_QUERY_END) ? 1 : 0;
-    // ---- the band does not widen with |ql - tl|, so a slot's formula is monotone in both lengths and the largest pair the bounds admit
-    // is the bounds themselves
-    const int cap_tl = std::min(max_tl, BANDED_MAX_LEN), cap_ql = std::min(max_ql, BANDED_MAX_LEN);
-    if (adaptive)
-        return launch_on_slots(ctx, st, a, extend_adaptive_pair_bytes(cap_tl, cap_ql, a.band, score_only), launch_extend_adaptive, "launch_extend_adaptive",
-                               MGL_SW_KERNEL_EXTEND_ADAPTIVE);
-    return launch_on_slots(ctx, st, a, extend_pair_bytes(cap_tl, cap_ql, a.band, score_only), launch_extend, "launch_extend", MGL_SW_KERNEL_EXTEND);
+    // ---- the slots are sized for the largest pair the bounds admit
+    const int64_t slot_bound = extend_slot_bound(adaptive, max_tl, max_ql, a.band, score_only);
+    if (adaptive) return launch_on_slots(stage, a, slot_bound, launch_extend_adaptive, "launch_extend_adaptive", MGL_SW_KERNEL_EXTEND_ADAPTIVE);
+    return launch_on_slots(stage, a, slot_bound, launch_extend, "launch_extend", MGL_SW_KERNEL_EXTEND);
 }
 
 } // extern "C"

@@ -2,7 +2,7 @@
 // that probes it (mgl_sw_seed_index_batch_device) and the stage that turns a read's chain into a window of the reference
 // (mgl_sw_locate_window_batch_device): include/mgl_sw.h, DESIGN.md section 9j.  Host side only: argument checks, the index's own
 // allocations, one workspace for the seed stage, launches on the caller's stream.  The build synchronises the stream -- it has to
-// learn the number of entries before it allocates them --; the two batch entries do not.  Its own translation unit, like sw_seed.cpp.
+// learn the number of entries before it allocates them --; the two batch entries do not.  The batch entries' frame is sw_stage_host.h's.
 #include "../../include/mgl_sw.h"
 
 #include <hip/hip_runtime.h>
@@ -11,10 +11,9 @@
 #include <cstdint>
 #include <mutex>
 #include <new>
-#include <string>
 
-#include "sw_ctx_access.h"
 #include "sw_index.h"
+#include "sw_stage_host.h"
 
 using namespace mgl_sw_dev;
 using namespace mgl_sw_host;
@@ -29,15 +28,6 @@ struct mgl_sw_index {
 };
 
 namespace {
-
-int refuse(mgl_sw_ctx *ctx, const char *entry, const char *bad)
-{
-    if (ctx) {
-        std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-        ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, (std::string(entry) + ": " + bad).c_str());
-    }
-    return MGL_SW_ERR_BAD_ARG;
-}
 
 // device memory that lives no longer than the build
 struct Scratch {
@@ -84,7 +74,7 @@ int mgl_sw_index_build_device(mgl_sw_ctx *ctx, void *stream, const uint8_t *d_re
     else if (k < SEED_MIN_K || k > SEED_MAX_K) bad = "k outside 4 .. 16";
     else if (w < 1 || w > SEED_MAX_W) bad = "w outside 1 .. 32";
     if (bad) return refuse(ctx, "mgl_sw_index_build_device", bad);
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
+    if (!ctx) return no_context();
     std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t he = hipSetDevice(ctx_device(ctx));
@@ -197,26 +187,23 @@ int mgl_sw_seed_index_batch_device(mgl_sw_ctx *ctx, void *stream, const mgl_sw_i
     else if (max_cand < 1 || max_cand > SEED_MAX_CAND) bad = "max_cand outside 1 .. 8192";
     else if (cand_capacity < 0 || cand_capacity > SEED_MAX_PAIRS) bad = "cand_capacity outside 0 .. 2^30";
     if (bad) return refuse(ctx, "mgl_sw_seed_index_batch_device", bad);
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
-    // there is no kernel id for this stage: the timing record keeps the fill_kernel it has (read before the context is locked)
-    mgl_sw_timing before{};
-    const int trc = mgl_sw_ctx_get_timing(ctx, &before);
-    if (trc != MGL_SW_OK) return trc;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!ctx) return no_context();
+    // there is no kernel id for this stage: the timing record keeps the fill_kernel it has (Stage's default)
+    Stage stage(ctx, stream);
+    hipStream_t st = stage.st;
     if (idx->device != ctx_device(ctx)) return ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, "mgl_sw_seed_index_batch_device: the index lives on another device");
 
     // ---- one workspace: the counts and the staging of the rows, then one slot per workgroup
     const int64_t rows = strands * n;
-    const int64_t limit = std::max<int64_t>(ctx_workspace_limit(ctx), 256) / 256 * 256;
+    const int64_t limit = stage.limit();
     const SeedWorkspace sg = seed_workspace(rows, max_cand);
     const int64_t room = limit - sg.bytes;
     if (room < sg.slot_bytes)
         return ctx_fail(ctx, MGL_SW_ERR_NOMEM,
                         "mgl_sw_seed_index_batch_device: the workspace limit does not hold the staging of the batch's rows beside a slot: split the batch");
     const int64_t groups = std::min(std::min<int64_t>(std::max<int64_t>(n, 1), (int64_t)ctx_cus(ctx) * SEED_GROUPS_PER_CU), room / sg.slot_bytes);
-    void *wsv = nullptr;
-    const int rc = ctx_borrow_workspace(ctx, st, (size_t)(sg.bytes + groups * sg.slot_bytes), &wsv);
+    unsigned char *ws = nullptr;
+    const int rc = stage.borrow((size_t)(sg.bytes + groups * sg.slot_bytes), &ws);
     if (rc != MGL_SW_OK) return rc;
 
     SeedIndexArgs aa{};
@@ -236,7 +223,7 @@ int mgl_sw_seed_index_batch_device(mgl_sw_ctx *ctx, void *stream, const mgl_sw_i
     a.max_occ = max_occ;
     a.merge = merge;
     a.max_cand = max_cand;
-    a.ws = static_cast<unsigned char *>(wsv);
+    a.ws = ws;
     a.groups = (int)groups;
     a.cand_start = d_cand_start_out;
     a.cand_t = d_cand_t_out;
@@ -244,19 +231,14 @@ int mgl_sw_seed_index_batch_device(mgl_sw_ctx *ctx, void *stream, const mgl_sw_i
     a.cand_len = d_cand_len_out;
     a.status = d_status_out;
 
-    // a step that fails behind others of this call: those still use the workspace, so it is returned before the error is
-    auto give_up = [&](hipError_t he, const char *where) {
-        ctx_return_workspace(ctx, st, before.fill_kernel, 0);
-        return ctx_hip_fail(ctx, he, where);
-    };
     hipError_t he = launch_seed_index(aa, st);
-    if (he != hipSuccess) return give_up(he, "launch_seed_index");
+    if (he != hipSuccess) return stage.fail(he, "launch_seed_index");
     // the scan and the pack of the seed stage read nothing but the rows' counts and staging: they serve these rows as they are
     he = launch_seed_scan(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_seed_scan");
+    if (he != hipSuccess) return stage.fail(he, "launch_seed_scan");
     he = launch_seed_pack(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_seed_pack");
-    return ctx_return_workspace(ctx, st, before.fill_kernel, 0);
+    if (he != hipSuccess) return stage.fail(he, "launch_seed_pack");
+    return stage.done();
 }
 
 int mgl_sw_locate_window_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, int64_t ref_len, const int32_t *d_q_len, const int64_t *d_anchor_start,
@@ -273,11 +255,10 @@ int mgl_sw_locate_window_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
     else if (max_tl < 1) bad = "max_tl below 1";
     else if (!d_t_start_out || !d_t_len_out || !d_anchor_t_out) bad = "null output array";
     if (bad) return refuse(ctx, "mgl_sw_locate_window_batch_device", bad);
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!ctx) return no_context();
+    Stage stage(ctx, stream);
     hipError_t he = hipSetDevice(ctx_device(ctx));
-    if (he != hipSuccess) return ctx_hip_fail(ctx, he, "hipSetDevice");
+    if (he != hipSuccess) return stage.fail(he, "hipSetDevice");
 
     LocateArgs a{};
     a.q_len = d_q_len;
@@ -294,9 +275,9 @@ int mgl_sw_locate_window_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
     a.t_len = d_t_len_out;
     a.anchor_t_out = d_anchor_t_out;
     a.status = d_status_out;
-    he = launch_locate_window(a, st);
-    if (he != hipSuccess) return ctx_hip_fail(ctx, he, "launch_locate_window");
-    return MGL_SW_OK;
+    he = launch_locate_window(a, stage.st);
+    if (he != hipSuccess) return stage.fail(he, "launch_locate_window");
+    return stage.done(); // (no workspace: the timing record is not touched)
 }
 
 } // extern "C"

@@ -1,8 +1,7 @@
 // sw_local.cpp -- mgl_sw_local_batch_device_matrix (include/mgl_sw.h): local Smith-Waterman with a substitution matrix.  Host side only:
 // argument checks, the planner rule, the workspace and the launches of the two kernels (sw_local_lane.hip: kernel A, the packed score
-// pass over tiles that share their target; sw_local.hip: kernel B, any pair in int32 with ends, begin and CIGAR).  Its own translation
-// unit: the context is reached through the accessors at the end of sw_capi.cpp (sw_ctx_access.h), so the host-sanitizer build of sw_capi.cpp (tests/cpp)
-// needs nothing of the new kernels.
+// pass over tiles that share their target; sw_local.hip: kernel B, any pair in int32 with ends, begin and CIGAR).  The entry's lock and
+// refusals are sw_stage_host.h's; the two runs keep their own workspace calls (a failed step of theirs leaves the workspace as it is).
 #include "../../include/mgl_sw.h"
 
 #include <hip/hip_runtime.h>
@@ -11,12 +10,10 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <string>
 #include <vector>
 
-#include "sw_ctx_access.h"
 #include "sw_local.h"
+#include "sw_stage_host.h"
 
 using namespace mgl_sw_dev;
 
@@ -120,15 +117,9 @@ int mgl_sw_local_batch_device_matrix(mgl_sw_ctx *ctx, void *stream, int64_t n, c
             if (code[k] >= MATRIX_DIM) bad = "code >= 32";
         if (gopen == INT32_MIN || gext == INT32_MIN || std::abs(gopen) > (1 << 24) || std::abs(gext) > (1 << 24)) bad = "gap penalty beyond 2^24";
     }
-    if (bad) {
-        if (ctx) {
-            std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-            ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, (std::string("mgl_sw_local_batch_device_matrix: ") + bad).c_str());
-        }
-        return MGL_SW_ERR_BAD_ARG;
-    }
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
+    if (bad) return refuse(ctx, "mgl_sw_local_batch_device_matrix", bad);
+    if (!ctx) return no_context();
+    Stage stage(ctx, stream);
     if (n == 0) return MGL_SW_OK;
     gopen = std::abs(gopen);
     gext = std::abs(gext);
@@ -137,7 +128,7 @@ int mgl_sw_local_batch_device_matrix(mgl_sw_ctx *ctx, void *stream, int64_t n, c
         smin = std::min<int>(smin, matrix[k]);
         smax = std::max<int>(smax, matrix[k]);
     }
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipStream_t st = stage.st;
     int8_t *dm = nullptr;
     uint8_t *dc = nullptr;
     LOCAL_TRY(ctx_stage_matrix(ctx, st, matrix, code, &dm, &dc));

@@ -2,19 +2,17 @@
 // every read out, ranked, with parents and mapping qualities.  Host side only: argument checks, one workspace
 // (the reads' anchor counts and, where the anchor outputs are wanted, the staging of the chains) and one launch on the caller's
 // stream -- sw_rank_chains_kernel -- or three: the chain stage's own prefix sum (launch_chain_dp_scan, as it is) and
-// sw_rank_pack_kernel behind it.  No synchronisation.  Its own translation unit, like sw_chain_dp.cpp.
+// sw_rank_pack_kernel behind it.  No synchronisation.  The entry's frame is sw_stage_host.h's.
 #include "../../include/mgl_sw.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
-#include <string>
 
 #include "sw_chain_dp.h"
-#include "sw_ctx_access.h"
 #include "sw_rank.h"
+#include "sw_stage_host.h"
 
 using namespace mgl_sw_dev;
 using namespace mgl_sw_host;
@@ -43,31 +41,21 @@ int mgl_sw_rank_chains_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, in
     else if (max_chains < 1 || max_chains > RANK_MAX_CHAINS) bad = "max_chains outside 1 .. 16";
     else if (min_score < 1 || min_cnt < 1) bad = "min_score or min_cnt < 1";
     else if (mask_level < 1 || mask_level > 256) bad = "mask_level outside 1 .. 256";
-    if (bad) {
-        if (ctx) {
-            std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-            ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, (std::string("mgl_sw_rank_chains_batch_device: ") + bad).c_str());
-        }
-        return MGL_SW_ERR_BAD_ARG;
-    }
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
-    // there is no kernel id for this stage: the timing record keeps the fill_kernel it has (read before the context is locked)
-    mgl_sw_timing before{};
-    const int trc = mgl_sw_ctx_get_timing(ctx, &before);
-    if (trc != MGL_SW_OK) return trc;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (bad) return refuse(ctx, "mgl_sw_rank_chains_batch_device", bad);
+    if (!ctx) return no_context();
+    // there is no kernel id for this stage: the timing record keeps the fill_kernel it has (Stage's default)
+    Stage stage(ctx, stream);
+    hipStream_t st = stage.st;
     const bool anchors = wanted == 4;
 
     // ---- one workspace: the counts and, for the anchor outputs, the staging of the whole batch
-    const int64_t limit = std::max<int64_t>(ctx_workspace_limit(ctx), 256) / 256 * 256;
+    const int64_t limit = stage.limit();
     const RankWorkspace wk = rank_workspace(n, total_cand, anchors);
     if (wk.bytes > limit)
         return ctx_fail(ctx, MGL_SW_ERR_NOMEM, "mgl_sw_rank_chains_batch_device: the workspace limit does not hold the batch's counts and staging: split the batch");
-    void *wsv = nullptr;
-    const int rc = ctx_borrow_workspace(ctx, st, (size_t)std::max<int64_t>(wk.bytes, 256), &wsv);
+    unsigned char *ws = nullptr;
+    const int rc = stage.borrow((size_t)std::max<int64_t>(wk.bytes, 256), &ws);
     if (rc != MGL_SW_OK) return rc;
-    unsigned char *const ws = static_cast<unsigned char *>(wsv);
 
     RankArgs a{};
     a.row_q_len = d_row_q_len;
@@ -98,24 +86,19 @@ int mgl_sw_rank_chains_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, in
     a.ranked_len = d_ranked_len_out;
     a.status = d_status_out;
 
-    // a step that fails behind others of this call: those still use the workspace, so it is returned before the error is
-    auto give_up = [&](hipError_t he, const char *where) {
-        ctx_return_workspace(ctx, st, before.fill_kernel, 0);
-        return ctx_hip_fail(ctx, he, where);
-    };
     hipError_t he = launch_rank_chains(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_rank_chains");
+    if (he != hipSuccess) return stage.fail(he, "launch_rank_chains");
     if (anchors) {
         ChainDpArgs scan{}; // the chain stage's prefix sum reads count and n and writes chain_start, nothing else
         scan.n = n;
         scan.count = a.count;
         scan.chain_start = d_ranked_start_out;
         he = launch_chain_dp_scan(scan, st);
-        if (he != hipSuccess) return give_up(he, "launch_chain_dp_scan");
+        if (he != hipSuccess) return stage.fail(he, "launch_chain_dp_scan");
         he = launch_rank_pack(a, st);
-        if (he != hipSuccess) return give_up(he, "launch_rank_pack");
+        if (he != hipSuccess) return stage.fail(he, "launch_rank_pack");
     }
-    return ctx_return_workspace(ctx, st, before.fill_kernel, 0);
+    return stage.done();
 }
 
 } // extern "C"

@@ -1,18 +1,16 @@
 // sw_seed.cpp -- mgl_sw_seed_batch_device (include/mgl_sw.h): reads and their windows in, candidate anchors out, in the CSR layout
 // mgl_sw_chain_anchors_batch_device reads.  Host side only: argument checks, one workspace (the counts, the staging
 // of the candidates, and one slot per workgroup for what outgrows its LDS) and three launches on the caller's stream -- sw_seed_kernel,
-// sw_seed_scan_kernel, sw_seed_pack_kernel.  No synchronisation.  Its own translation unit, like sw_chain_dp.cpp.
+// sw_seed_scan_kernel, sw_seed_pack_kernel.  No synchronisation.  The entry's frame is sw_stage_host.h's.
 #include "../../include/mgl_sw.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
-#include <string>
 
-#include "sw_ctx_access.h"
 #include "sw_seed.h"
+#include "sw_stage_host.h"
 
 using namespace mgl_sw_dev;
 using namespace mgl_sw_host;
@@ -36,32 +34,22 @@ int mgl_sw_seed_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uin
     else if (merge != 0 && merge != 1) bad = "merge is neither 0 nor 1";
     else if (max_cand < 1 || max_cand > SEED_MAX_CAND) bad = "max_cand outside 1 .. 8192";
     else if (cand_capacity < 0 || cand_capacity > SEED_MAX_PAIRS) bad = "cand_capacity outside 0 .. 2^30";
-    if (bad) {
-        if (ctx) {
-            std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-            ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, (std::string("mgl_sw_seed_batch_device: ") + bad).c_str());
-        }
-        return MGL_SW_ERR_BAD_ARG;
-    }
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
-    // there is no kernel id for this stage: the timing record keeps the fill_kernel it has (read before the context is locked)
-    mgl_sw_timing before{};
-    const int trc = mgl_sw_ctx_get_timing(ctx, &before);
-    if (trc != MGL_SW_OK) return trc;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (bad) return refuse(ctx, "mgl_sw_seed_batch_device", bad);
+    if (!ctx) return no_context();
+    // there is no kernel id for this stage: the timing record keeps the fill_kernel it has (Stage's default)
+    Stage stage(ctx, stream);
+    hipStream_t st = stage.st;
 
     // ---- one workspace: the counts and the staging of the whole batch, then one slot per workgroup
-    const int64_t limit = std::max<int64_t>(ctx_workspace_limit(ctx), 256) / 256 * 256;
+    const int64_t limit = stage.limit();
     const SeedWorkspace sg = seed_workspace(n, max_cand);
     const int64_t room = limit - sg.bytes;
     if (room < sg.slot_bytes)
         return ctx_fail(ctx, MGL_SW_ERR_NOMEM, "mgl_sw_seed_batch_device: the workspace limit does not hold the batch's staging beside a slot: split the batch");
     const int64_t groups = std::min(std::min<int64_t>(std::max<int64_t>(n, 1), (int64_t)ctx_cus(ctx) * SEED_GROUPS_PER_CU), room / sg.slot_bytes);
-    void *wsv = nullptr;
-    const int rc = ctx_borrow_workspace(ctx, st, (size_t)(sg.bytes + groups * sg.slot_bytes), &wsv);
+    unsigned char *ws = nullptr;
+    const int rc = stage.borrow((size_t)(sg.bytes + groups * sg.slot_bytes), &ws);
     if (rc != MGL_SW_OK) return rc;
-    unsigned char *const ws = static_cast<unsigned char *>(wsv);
 
     SeedStageArgs a{};
     a.targets = d_targets;
@@ -85,18 +73,13 @@ int mgl_sw_seed_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uin
     a.cand_len = d_cand_len_out;
     a.status = d_status_out;
 
-    // a step that fails behind others of this call: those still use the workspace, so it is returned before the error is
-    auto give_up = [&](hipError_t he, const char *where) {
-        ctx_return_workspace(ctx, st, before.fill_kernel, 0);
-        return ctx_hip_fail(ctx, he, where);
-    };
     hipError_t he = launch_seed(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_seed");
+    if (he != hipSuccess) return stage.fail(he, "launch_seed");
     he = launch_seed_scan(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_seed_scan");
+    if (he != hipSuccess) return stage.fail(he, "launch_seed_scan");
     he = launch_seed_pack(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_seed_pack");
-    return ctx_return_workspace(ctx, st, before.fill_kernel, 0);
+    if (he != hipSuccess) return stage.fail(he, "launch_seed_pack");
+    return stage.done();
 }
 
 } // extern "C"

@@ -2,15 +2,13 @@
 // (DESIGN.md section 9e).  Host side only: argument checks, one workspace for the staging of a chunk of pairs and the extension
 // kernels' slots, and per chunk four launches on the caller's stream -- sw_seed_split_kernel, the extension kernel over the left
 // flanks and over the right ones (sw_extend.hip or sw_extend_adaptive.hip, as they are), sw_seed_join_kernel.  No synchronisation.
-// Its own translation unit, like sw_extend.cpp: the context is reached through sw_ctx_access.h.
+// The entry's frame is sw_stage_host.h's, the two sides' extension sw_band_host.h's.
 #include "../../include/mgl_sw.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
-#include <string>
 
 #include "sw_band_host.h"
 #include "sw_seed_extend.h"
@@ -31,7 +29,6 @@ int mgl_sw_extend_seed_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
                                     int32_t *d_cigar_len_out, int32_t *d_status_out, int flags)
 {
     const bool score_only = (flags & MGL_SW_FLAG_SCORE_ONLY) != 0, binary = (flags & MGL_SW_FLAG_BINARY_CIGAR) != 0;
-    const bool adaptive = (flags & MGL_SW_FLAG_EXTEND_ADAPTIVE_BAND) != 0;
     // ---- arguments first: nothing below touches a device before they are known good
     const char *bad = nullptr;
     if (n < 0) bad = "n < 0";
@@ -41,41 +38,22 @@ int mgl_sw_extend_seed_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
     else if (band < 0) bad = "band < 0";
     else if (max_tl < 1 || max_ql < 1) bad = "max_tl / max_ql < 1";
     else if (!score_only && (!d_cigar_out || !d_cigar_len_out || cigar_stride < (binary ? 4 : 2))) bad = "CIGAR array missing or cigar_stride too small";
-    if (bad) {
-        if (ctx) {
-            std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-            ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, (std::string("mgl_sw_extend_seed_batch_device: ") + bad).c_str());
-        }
-        return MGL_SW_ERR_BAD_ARG;
-    }
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
+    if (bad) return refuse(ctx, "mgl_sw_extend_seed_batch_device", bad);
+    if (!ctx) return no_context();
+    Stage stage(ctx, stream);
     if (n == 0) return MGL_SW_OK;
     mgl_sw_normalize_params(&match, &mismatch, &gopen, &gext);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipStream_t st = stage.st;
 
-    // ---- the extension of one side: the extend entry's arguments, band clamp and slot bound (sw_extend.cpp); a flank is shorter than
-    // its pair, so the caller's bounds hold for it
+    // ---- the extension of one side (sw_band_host.h)
     ExtendArgs e{};
-    e.match = match;
-    e.mismatch = mismatch;
-    e.gopen = gopen;
-    e.gext = gext;
-    e.band = adaptive ? (int)std::min<int64_t>({(int64_t)band, (int64_t)max_tl + max_ql, 2 * (int64_t)BANDED_MAX_LEN}) : clamp_band(band, max_tl, max_ql);
-    e.zdrop = zdrop;
-    e.max_tl = max_tl;
-    e.max_ql = max_ql;
-    e.binary_cigar = 1; // the internal rows: the join reads elements, not text
-    e.score_only = score_only ? 1 : 0;
-    e.to_query_end = (flags & MGL_SW_FLAG_EXTEND_TO_QUERY_END) ? 1 : 0;
-    const int cap_tl = std::min(max_tl, BANDED_MAX_LEN), cap_ql = std::min(max_ql, BANDED_MAX_LEN);
-    const int64_t slot_bound = adaptive ? extend_adaptive_pair_bytes(cap_tl, cap_ql, e.band, score_only) : extend_pair_bytes(cap_tl, cap_ql, e.band, score_only);
+    const int64_t slot_bound = extend_sides_setup(stage, e, match, mismatch, gopen, gext, flags, band, zdrop, max_tl, max_ql);
 
     // ---- one workspace: the staging of a chunk of m pairs, then one slot per wave.  All n pairs are staged at once where that takes
     // at most half the limit (the slots, which set the number of waves, keep the other half).  Otherwise the batch is worked off in
     // chunks of m pairs, m the most whose staging half the limit holds: a pair's exact bytes, and 256 bytes of rounding for each part.
     // Where half the limit does not hold one pair, m is 1 and that pair's staging takes more than half; the slot gets what is left
-    const int64_t limit = std::max<int64_t>(ctx_workspace_limit(ctx), 256) / 256 * 256;
+    const int64_t limit = stage.limit();
     auto staged = [&](int64_t m) { return seed_staging(m, max_tl, max_ql, cigar_stride, binary, score_only).bytes; };
     const int64_t per_pair = seed_staging_pair_bytes(seed_staging(1, max_tl, max_ql, cigar_stride, binary, score_only));
     int64_t m = std::min(n, SEED_MAX_CHUNK);
@@ -84,10 +62,9 @@ int mgl_sw_extend_seed_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
     if (slot < 256) return ctx_fail(ctx, MGL_SW_ERR_NOMEM, "mgl_sw_extend_seed_batch_device: the workspace limit does not hold the staging of one pair beside a slot");
     const SeedStaging sg = seed_staging(m, max_tl, max_ql, cigar_stride, binary, score_only);
     const int64_t waves = std::max<int64_t>(1, std::min<int64_t>({m, (int64_t)ctx_cus(ctx) * BANDED_WAVES_PER_CU, (limit - sg.bytes) / slot}));
-    void *wsv = nullptr;
-    const int rc = ctx_borrow_workspace(ctx, st, (size_t)(sg.bytes + waves * slot), &wsv);
+    unsigned char *ws = nullptr;
+    const int rc = stage.borrow((size_t)(sg.bytes + waves * slot), &ws);
     if (rc != MGL_SW_OK) return rc;
-    unsigned char *const ws = static_cast<unsigned char *>(wsv);
     e.ws = ws + sg.bytes;
     e.slot_bytes = slot;
     e.slots = (int)waves;
@@ -100,35 +77,11 @@ int mgl_sw_extend_seed_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
     s.max_ql = max_ql;
     s.match = match;
     s.mismatch = mismatch;
-    s.rev_t = ws + sg.rev_t;
-    s.rev_q = ws + sg.rev_q;
-    s.tstride = sg.tstride;
-    s.qstride = sg.qstride;
-    for (int x = 0; x < 4; ++x) {
-        s.off[x] = reinterpret_cast<int64_t *>(ws + sg.off[x]);
-        s.len[x] = reinterpret_cast<int32_t *>(ws + sg.len[x]);
-    }
-    s.flank = reinterpret_cast<int4 *>(ws + sg.flank);
-    for (int x = 0; x < 2; ++x) {
-        s.side_ext[x] = reinterpret_cast<const Extension *>(ws + sg.ext[x]);
-        s.side_status[x] = reinterpret_cast<const int32_t *>(ws + sg.status[x]);
-        s.side_clen[x] = reinterpret_cast<const int32_t *>(ws + sg.clen[x]);
-        s.side_cigar[x] = score_only ? nullptr : reinterpret_cast<const uint32_t *>(ws + sg.cigar[x]);
-    }
-    s.istride = sg.istride;
+    bind_seed_staging(s, ws, sg, score_only);
     s.cigar_stride = cigar_stride;
     s.binary_cigar = binary ? 1 : 0;
     s.score_only = score_only ? 1 : 0;
 
-    auto launch_side = adaptive ? launch_extend_adaptive : launch_extend;
-    const int fill = adaptive ? MGL_SW_KERNEL_EXTEND_ADAPTIVE : MGL_SW_KERNEL_EXTEND;
-    int launches = 0;
-    // a launch that fails behind others of this call: those still use the workspace, so it is returned (the next call on another
-    // stream waits for them) before the error is
-    auto give_up = [&](hipError_t he, const char *where) {
-        ctx_return_workspace(ctx, st, fill, launches);
-        return ctx_hip_fail(ctx, he, where);
-    };
     for (int64_t c = 0; c < n; c += m) {
         s.n = e.n = std::min(m, n - c);
         s.t_start = d_t_start + c;
@@ -145,22 +98,13 @@ int mgl_sw_extend_seed_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, co
         s.cigar_len = d_cigar_len_out ? d_cigar_len_out + c : nullptr;
         s.status = d_status_out ? d_status_out + c : nullptr;
         hipError_t he = launch_seed_split(s, st);
-        if (he != hipSuccess) return give_up(he, "launch_seed_split");
-        for (int side = 0; side < 2; ++side) { // 0: the reversed copies of the left flanks; 1: the right flanks in the caller's arrays
-            e.t = SeqSet{side ? d_targets : s.rev_t, s.off[2 * side], s.len[2 * side], max_tl, 0};
-            e.q = SeqSet{side ? d_queries : s.rev_q, s.off[2 * side + 1], s.len[2 * side + 1], max_ql, 0};
-            e.ext = reinterpret_cast<Extension *>(ws + sg.ext[side]);
-            e.status = reinterpret_cast<int32_t *>(ws + sg.status[side]);
-            e.cigar = score_only ? nullptr : reinterpret_cast<char *>(ws + sg.cigar[side]);
-            e.cigar_len = reinterpret_cast<int32_t *>(ws + sg.clen[side]);
-            he = launch_side(e, st);
-            if (he != hipSuccess) return give_up(he, adaptive ? "launch_extend_adaptive" : "launch_extend");
-            ++launches;
-        }
+        if (he != hipSuccess) return stage.fail(he, "launch_seed_split");
+        const int src = launch_extend_sides(stage, e, s, ws, sg);
+        if (src != MGL_SW_OK) return src;
         he = launch_seed_join(s, st);
-        if (he != hipSuccess) return give_up(he, "launch_seed_join");
+        if (he != hipSuccess) return stage.fail(he, "launch_seed_join");
     }
-    return ctx_return_workspace(ctx, st, fill, launches);
+    return stage.done();
 }
 
 } // extern "C"

@@ -1,34 +1,19 @@
 // sw_seed_strands.cpp -- mgl_sw_seed_strands_batch_device and mgl_sw_select_strand_batch_device (include/mgl_sw.h): the seed stage over
 // both orientations of every read, as 2n rows for mgl_sw_chain_anchors_batch_device, and the choice of a read's strand behind that
 // stage, as arguments for mgl_sw_align_chain_batch_device.  Host side only: argument checks, one workspace and
-// three launches on the caller's stream each.  No synchronisation.  Its own translation unit, like sw_seed.cpp.
+// three launches on the caller's stream each.  No synchronisation.  The entries' frame is sw_stage_host.h's.
 #include "../../include/mgl_sw.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
-#include <string>
 
-#include "sw_ctx_access.h"
 #include "sw_seed_strands.h"
+#include "sw_stage_host.h"
 
 using namespace mgl_sw_dev;
 using namespace mgl_sw_host;
-
-namespace {
-
-int refuse(mgl_sw_ctx *ctx, const char *entry, const char *bad)
-{
-    if (ctx) {
-        std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-        ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, (std::string(entry) + ": " + bad).c_str());
-    }
-    return MGL_SW_ERR_BAD_ARG;
-}
-
-} // namespace
 
 extern "C" {
 
@@ -51,25 +36,22 @@ int mgl_sw_seed_strands_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, c
     else if (max_cand < 1 || max_cand > SEED_MAX_CAND) bad = "max_cand outside 1 .. 8192";
     else if (cand_capacity < 0 || cand_capacity > SEED_MAX_PAIRS) bad = "cand_capacity outside 0 .. 2^30";
     if (bad) return refuse(ctx, "mgl_sw_seed_strands_batch_device", bad);
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
-    // there is no kernel id for this stage: the timing record keeps the fill_kernel it has (read before the context is locked)
-    mgl_sw_timing before{};
-    const int trc = mgl_sw_ctx_get_timing(ctx, &before);
-    if (trc != MGL_SW_OK) return trc;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!ctx) return no_context();
+    // there is no kernel id for this stage: the timing record keeps the fill_kernel it has (Stage's default)
+    Stage stage(ctx, stream);
+    hipStream_t st = stage.st;
 
     // ---- one workspace: the counts and the staging of the 2n rows, then one slot of two halves per workgroup
     const int64_t rows = 2 * n;
-    const int64_t limit = std::max<int64_t>(ctx_workspace_limit(ctx), 256) / 256 * 256;
+    const int64_t limit = stage.limit();
     const SeedWorkspace sg = seed_workspace(rows, max_cand);
     const int64_t slot_bytes = 2 * (int64_t)sg.slot_bytes, room = limit - sg.bytes;
     if (room < slot_bytes)
         return ctx_fail(ctx, MGL_SW_ERR_NOMEM,
                         "mgl_sw_seed_strands_batch_device: the workspace limit does not hold the staging of the batch's 2n rows beside a slot: split the batch");
     const int64_t groups = std::min(std::min<int64_t>(std::max<int64_t>(n, 1), (int64_t)ctx_cus(ctx) * SEED_GROUPS_PER_CU), room / slot_bytes);
-    void *wsv = nullptr;
-    const int rc = ctx_borrow_workspace(ctx, st, (size_t)(sg.bytes + groups * slot_bytes), &wsv);
+    unsigned char *ws = nullptr;
+    const int rc = stage.borrow((size_t)(sg.bytes + groups * slot_bytes), &ws);
     if (rc != MGL_SW_OK) return rc;
 
     SeedStrandsArgs aa{};
@@ -87,7 +69,7 @@ int mgl_sw_seed_strands_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, c
     a.max_occ = max_occ;
     a.merge = merge;
     a.max_cand = max_cand;
-    a.ws = static_cast<unsigned char *>(wsv);
+    a.ws = ws;
     a.groups = (int)groups;
     a.cand_start = d_cand_start_out;
     a.cand_t = d_cand_t_out;
@@ -97,19 +79,14 @@ int mgl_sw_seed_strands_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, c
     aa.row_t_len = d_row_t_len_out;
     aa.row_q_len = d_row_q_len_out;
 
-    // a step that fails behind others of this call: those still use the workspace, so it is returned before the error is
-    auto give_up = [&](hipError_t he, const char *where) {
-        ctx_return_workspace(ctx, st, before.fill_kernel, 0);
-        return ctx_hip_fail(ctx, he, where);
-    };
     hipError_t he = launch_seed_strands(aa, st);
-    if (he != hipSuccess) return give_up(he, "launch_seed_strands");
+    if (he != hipSuccess) return stage.fail(he, "launch_seed_strands");
     // the scan and the pack of the seed stage read nothing but the rows' counts and staging: they serve the 2n rows as they are
     he = launch_seed_scan(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_seed_scan");
+    if (he != hipSuccess) return stage.fail(he, "launch_seed_scan");
     he = launch_seed_pack(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_seed_pack");
-    return ctx_return_workspace(ctx, st, before.fill_kernel, 0);
+    if (he != hipSuccess) return stage.fail(he, "launch_seed_pack");
+    return stage.done();
 }
 
 int mgl_sw_select_strand_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_queries, const int64_t *d_q_start,
@@ -127,19 +104,16 @@ int mgl_sw_select_strand_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
     else if (!d_strand_out || !d_queries_out) bad = "null strand or query output";
     else if (!d_anchor_start_out || !d_anchor_t_out || !d_anchor_q_out || !d_anchor_len_out) bad = "null anchor array";
     if (bad) return refuse(ctx, "mgl_sw_select_strand_batch_device", bad);
-    if (!ctx) return mgl_sw_device_count() <= 0 ? MGL_SW_ERR_DEVICE : MGL_SW_ERR_BAD_ARG;
-    mgl_sw_timing before{};
-    const int trc = mgl_sw_ctx_get_timing(ctx, &before);
-    if (trc != MGL_SW_OK) return trc;
-    std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!ctx) return no_context();
+    Stage stage(ctx, stream);
+    hipStream_t st = stage.st;
 
     // ---- the workspace: K_p per pair
-    const int64_t limit = std::max<int64_t>(ctx_workspace_limit(ctx), 256) / 256 * 256;
+    const int64_t limit = stage.limit();
     const int64_t bytes = seed_ws_round(std::max<int64_t>(n, 1) * 4, 256);
     if (bytes > limit) return ctx_fail(ctx, MGL_SW_ERR_NOMEM, "mgl_sw_select_strand_batch_device: the workspace limit does not hold 4 bytes per pair");
-    void *wsv = nullptr;
-    const int rc = ctx_borrow_workspace(ctx, st, (size_t)bytes, &wsv);
+    unsigned char *ws = nullptr;
+    const int rc = stage.borrow((size_t)bytes, &ws);
     if (rc != MGL_SW_OK) return rc;
 
     SelectStrandArgs a{};
@@ -154,7 +128,7 @@ int mgl_sw_select_strand_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
     a.n = n;
     a.total_chain = total_chain;
     a.query_bytes = query_bytes;
-    a.count = static_cast<int32_t *>(wsv);
+    a.count = reinterpret_cast<int32_t *>(ws);
     a.strand = d_strand_out;
     a.queries_out = d_queries_out;
     a.anchor_start = d_anchor_start_out;
@@ -164,17 +138,13 @@ int mgl_sw_select_strand_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
     a.score = d_score_out;
     a.status = d_status_out;
 
-    auto give_up = [&](hipError_t he, const char *where) {
-        ctx_return_workspace(ctx, st, before.fill_kernel, 0);
-        return ctx_hip_fail(ctx, he, where);
-    };
     hipError_t he = launch_select_strand(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_select_strand");
+    if (he != hipSuccess) return stage.fail(he, "launch_select_strand");
     he = launch_select_strand_scan(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_select_strand_scan");
+    if (he != hipSuccess) return stage.fail(he, "launch_select_strand_scan");
     he = launch_select_strand_pack(a, st);
-    if (he != hipSuccess) return give_up(he, "launch_select_strand_pack");
-    return ctx_return_workspace(ctx, st, before.fill_kernel, 0);
+    if (he != hipSuccess) return stage.fail(he, "launch_select_strand_pack");
+    return stage.done();
 }
 
 } // extern "C"

@@ -67,10 +67,9 @@ class Index:
         import torch
 
         m = self.info.entries
-        keys, pos = torch.empty(m, dtype=torch.int32, device=self.ref.device), torch.empty(m, dtype=torch.int32, device=self.ref.device)
-        spare = torch.empty(2, dtype=torch.int64, device=self.ref.device)  # an empty tensor has no address: the entry wants one
-        _check(_lib.lib().mgl_sw_index_export_device(self.handle, torch.cuda.current_stream(self.ref.device).cuda_stream, keys.data_ptr() or spare.data_ptr(),
-                                                     pos.data_ptr() or spare.data_ptr(), m))
+        new, ptr = _alloc(self.ref.device), _ptrs(self.ref.device)
+        keys, pos = new(m), new(m)
+        _check(_lib.lib().mgl_sw_index_export_device(self.handle, torch.cuda.current_stream(self.ref.device).cuda_stream, ptr(keys), ptr(pos), m))
         return keys.view(torch.uint32), pos
 
     def close(self):
@@ -142,13 +141,11 @@ def _default_stride(max_tl, max_ql, binary_cigar):
 
 def _pack_pairs(refs, alts, dev, cigar_stride, binary_cigar):
     """Lists of byte strings -> (n, the six device tensors and two bounds the *_device forms take, cigar_stride)."""
-    import torch
-
     ts, qs = [bytes(x) for x in refs], [bytes(x) for x in alts]
     assert len(qs) == len(ts)
     td, toff = concat(ts)
     qd, qoff = concat(qs)
-    g = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+    g = lambda x: _upload(x, dev)  # noqa: E731
     tlen, qlen = np.diff(toff).astype(np.int32), np.diff(qoff).astype(np.int32)
     max_tl, max_ql = int(tlen.max(initial=1)), int(qlen.max(initial=1))
     if cigar_stride is None:
@@ -168,6 +165,109 @@ def _fetch(out, dev, return_status):
         k = int(np.flatnonzero(st)[0])
         raise _lib.MglSwError(int(st[k]), f"pair {k}")
     return out
+
+
+def _ptrs(dev, keep_null=False):
+    """-> ptr(x): the address of tensor ``x`` as a C entry takes it, None for None.  An empty tensor has no address and the entries
+    want one: it gets that of a spare tensor on ``dev``, made when the first empty one is met.  ``keep_null``: the older forms
+    (banded, extend, extend_seed, align_chain) pass an empty tensor's null address on as it is."""
+    if keep_null:
+        return lambda x: None if x is None else x.data_ptr()
+    spare = None
+
+    def spare_ptr():
+        nonlocal spare
+        if spare is None:
+            import torch
+
+            spare = torch.empty(2, dtype=torch.int64, device=dev)
+        return spare.data_ptr()
+
+    return lambda x: None if x is None else (x.data_ptr() or spare_ptr())  # (the expression the entries are called through)
+
+
+def _alloc(dev):
+    """-> new(shape, dtype=torch.int32): an uninitialised output tensor on ``dev``."""
+    import torch
+
+    return lambda shape, dtype=torch.int32: torch.empty(shape, dtype=dtype, device=dev)
+
+
+def _upload(x, dev, dtype=None):
+    """A host array (or list) as a contiguous tensor on ``dev``."""
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dtype))).to(dev)
+
+
+def _extend_flags(binary_cigar, score_only, to_query_end=False, adaptive_band=False):
+    return ((_lib.FLAG_BINARY_CIGAR if binary_cigar else 0) | (_lib.FLAG_SCORE_ONLY if score_only else 0) |
+            (_lib.FLAG_EXTEND_TO_QUERY_END if to_query_end else 0) | (_lib.FLAG_EXTEND_ADAPTIVE_BAND if adaptive_band else 0))
+
+
+def _csr(lists):
+    """Ragged lists of (t, q, l) -> (start int64 [len + 1], flat int32 [total, 3]): the CSR layout the stages take."""
+    start = np.zeros(len(lists) + 1, np.int64)
+    if lists:
+        np.cumsum([len(c) for c in lists], out=start[1:])
+    return start, np.asarray([a for c in lists for a in c], dtype=np.int32).reshape(-1, 3)
+
+
+def _candidate_lists(start, t, q, l, rows):
+    """The CSR arrays a stage wrote -> per row its list of (t, q, l)."""
+    return [[(int(t[i]), int(q[i]), int(l[i])) for i in range(start[r], start[r + 1])] for r in range(rows)]
+
+
+def _seed_rows(out, rows, cand_capacity, dev):
+    """The tuple of the seed stages that work on rows -- (cand_start [rows + 1] int64, cand_t, cand_q, cand_len [cand_capacity],
+    row_t_len, row_q_len, status [rows] int32; the last three may be None in a caller's) --, made where ``out`` is None, and checked."""
+    import torch
+
+    if out is None:
+        new = _alloc(dev)
+        out = (new(rows + 1, torch.int64), new(cand_capacity), new(cand_capacity), new(cand_capacity), new(rows), new(rows), new(rows))
+    cs, ct, cq, cl, rt, rq, st = out
+    assert min(ct.numel(), cq.numel(), cl.numel()) >= cand_capacity and cs.numel() >= rows + 1
+    assert all(x is None or x.numel() >= rows for x in (rt, rq, st))
+    return out
+
+
+def _pack_reads(reads, dev):
+    """A list of byte strings -> (n, the (queries, q_start, q_len) device tensors, the longest read)."""
+    qs = [bytes(q) for q in reads]
+    n, packed, _ = _pack_pairs(qs, qs, dev, 16, False)
+    return n, packed[3:6], packed[7]
+
+
+def _map_setup(reads, dev, slack, max_tl, stages):
+    """What the list-form mappers do before their device form: -> (n, the reads' tensors, max_tl, max_ql, the CIGAR stride, which
+    leaves ``stages``).  ``max_tl`` defaults to 1.5 times the longest read and the slack to either side."""
+    n, packed, max_ql = _pack_reads(reads, dev)
+    if max_tl is None:
+        max_tl = max_ql + max_ql // 2 + 2 * int(slack)
+    stride = stages.pop("cigar_stride", None) or _default_stride(max_tl, max_ql, False)
+    return n, packed, max_tl, max_ql, stride
+
+
+def _map_fields(n, stride, chosen, window, aln):
+    """The device tuples of a mapper, read back (the stream is done) -> (MapResult's six fields, ok, the alignments' records):
+    a read whose alignment has a status has zeros and an empty CIGAR, and the window's status where that refused the read."""
+    rec, cg, ln, st = aln[0].cpu().numpy(), aln[4].cpu().numpy().reshape(n, stride), aln[5].cpu().numpy(), aln[6].cpu().numpy()
+    t_start, wst = window[0].cpu().numpy(), window[3].cpu().numpy()
+    ok = st == 0
+    strand = chosen[0].cpu().numpy() if chosen is not None else np.zeros(n, np.int32)
+    ln = np.where(ok, ln, 0).astype(np.int32)
+    fields = (np.where(ok, t_start + rec[:, 1], 0), np.where(ok, t_start + rec[:, 2], 0), np.where(ok, strand, 0).astype(np.int32),
+              np.where(ok, rec[:, 0], 0).astype(np.int32), CigarColumn(cg, ln), np.where(wst != 0, wst, st).astype(np.int32))
+    return fields, ok, rec
+
+
+def _rank_fields(n, ranked):
+    """The ranking's device tuple, read back -> (mapq, n_chains, secondary) as RankedMapResult has them."""
+    nc, rr = ranked[0].cpu().numpy(), ranked[1].cpu().numpy()
+    mapq = np.asarray([int(rr[p, 0, 10]) if nc[p] > 0 else 0 for p in range(n)], dtype=np.int32)
+    secondary = [[(int(c[3]), int(c[4]), int(c[1]), int(c[0]), int(c[7])) for c in rr[p, 1:nc[p]]] for p in range(n)]
+    return mapq, nc.astype(np.int32), secondary
 
 
 class MicrosoftSmithWaterman:
@@ -267,13 +367,12 @@ class MicrosoftSmithWaterman:
         if cigar_stride is None:
             cigar_stride = _default_stride(max_tl, max_ql, binary_cigar)
         if out is None:
-            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 6), dtype=torch.int32, device=dev),
-                   None if score_only else torch.empty(n * cigar_stride, dtype=torch.uint8, device=dev),
-                   None if score_only else torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+            new = _alloc(dev)
+            out = (new(n), new((n, 6)), None if score_only else new(n * cigar_stride, torch.uint8), None if score_only else new(n), new(n))
         off, sc, cg, ln, st = out
         p = SWParameters(*parameters)
-        flags = (_lib.FLAG_BINARY_CIGAR if binary_cigar else 0) | (_lib.FLAG_SCORE_ONLY if score_only else 0)
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        flags = _extend_flags(binary_cigar, score_only)
+        ptr = _ptrs(dev, keep_null=True)
         rc = _lib.lib().mgl_sw_align_batch_device_banded(
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len),
             int(max_tl), int(max_ql), p.match, p.mismatch, p.gap_open, p.gap_extend, int(overhang_strategy), int(band), ptr(off), ptr(sc), ptr(cg),
@@ -313,13 +412,12 @@ class MicrosoftSmithWaterman:
         if cigar_stride is None:
             cigar_stride = _default_stride(max_tl, max_ql, binary_cigar)
         if out is None:
-            out = (torch.empty((n, 8), dtype=torch.int32, device=dev), None if score_only else torch.empty(n * cigar_stride, dtype=torch.uint8, device=dev),
-                   None if score_only else torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+            new = _alloc(dev)
+            out = (new((n, 8)), None if score_only else new(n * cigar_stride, torch.uint8), None if score_only else new(n), new(n))
         ext, cg, ln, st = out
         p = SWParameters(*parameters)
-        flags = ((_lib.FLAG_BINARY_CIGAR if binary_cigar else 0) | (_lib.FLAG_SCORE_ONLY if score_only else 0) |
-                 (_lib.FLAG_EXTEND_TO_QUERY_END if to_query_end else 0) | (_lib.FLAG_EXTEND_ADAPTIVE_BAND if adaptive_band else 0))
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        flags = _extend_flags(binary_cigar, score_only, to_query_end, adaptive_band)
+        ptr = _ptrs(dev, keep_null=True)
         rc = _lib.lib().mgl_sw_extend_batch_device(
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len),
             int(max_tl), int(max_ql), p.match, p.mismatch, p.gap_open, p.gap_extend, int(band), int(zdrop), ptr(ext), ptr(cg), int(cigar_stride),
@@ -341,7 +439,7 @@ class MicrosoftSmithWaterman:
         dev = torch.device("cuda", self._device)
         n, packed, cigar_stride = _pack_pairs(refs, alts, dev, cigar_stride, binary_cigar)
         sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.int32).reshape(n, 3).T)
-        seed_t, seed_q, seed_len = (torch.from_numpy(sd[c].copy()).to(dev) for c in range(3))
+        seed_t, seed_q, seed_len = (_upload(sd[c], dev) for c in range(3))
         out = self.extend_seed_device(*packed[:6], seed_t, seed_q, seed_len, *packed[6:], band, zdrop, parameters, to_query_end, cigar_stride,
                                       binary_cigar, score_only, adaptive_band=adaptive_band, sides=return_sides)
         aln, left, right, cg, ln, st = _fetch(out, dev, return_status)
@@ -365,15 +463,13 @@ class MicrosoftSmithWaterman:
         if cigar_stride is None:
             cigar_stride = _default_stride(max_tl, max_ql, binary_cigar)
         if out is None:
-            rec = lambda: torch.empty((n, 8), dtype=torch.int32, device=dev)  # noqa: E731
-            out = (rec(), rec() if sides else None, rec() if sides else None,
-                   None if score_only else torch.empty(n * cigar_stride, dtype=torch.uint8, device=dev),
-                   None if score_only else torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+            new = _alloc(dev)
+            out = (new((n, 8)), new((n, 8)) if sides else None, new((n, 8)) if sides else None,
+                   None if score_only else new(n * cigar_stride, torch.uint8), None if score_only else new(n), new(n))
         aln, left, right, cg, ln, st = out
         p = SWParameters(*parameters)
-        flags = ((_lib.FLAG_BINARY_CIGAR if binary_cigar else 0) | (_lib.FLAG_SCORE_ONLY if score_only else 0) |
-                 (_lib.FLAG_EXTEND_TO_QUERY_END if to_query_end else 0) | (_lib.FLAG_EXTEND_ADAPTIVE_BAND if adaptive_band else 0))
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        flags = _extend_flags(binary_cigar, score_only, to_query_end, adaptive_band)
+        ptr = _ptrs(dev, keep_null=True)
         rc = _lib.lib().mgl_sw_extend_seed_batch_device(
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len),
             ptr(seed_t), ptr(seed_q), ptr(seed_len), int(max_tl), int(max_ql), p.match, p.mismatch, p.gap_open, p.gap_extend, int(band), int(zdrop),
@@ -396,17 +492,14 @@ class MicrosoftSmithWaterman:
         dev = torch.device("cuda", self._device)
         n, packed, cigar_stride = _pack_pairs(refs, alts, dev, cigar_stride, binary_cigar)
         assert len(chains) == n
-        start = np.zeros(n + 1, np.int64)
-        if n:
-            np.cumsum([len(c) for c in chains], out=start[1:])
-        flat = np.asarray([a for c in chains for a in c], dtype=np.int32).reshape(-1, 3)
+        start, flat = _csr(chains)
         if max_gap is None:
             gt = gq = 0
             for c in chains:
                 for (st, sq, sl), (nt, nq, _) in zip(c, c[1:]):
                     gt, gq = max(gt, nt - st - sl), max(gq, nq - sq - sl)
             max_gap = (max(gt, 0), max(gq, 0))
-        g = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+        g = lambda x: _upload(x, dev)  # noqa: E731
         out = self.align_chain_device(*packed[:6], g(start), g(flat[:, 0]), g(flat[:, 1]), g(flat[:, 2]), *packed[6:], max_gap[0], max_gap[1], band, zdrop,
                                       parameters, to_query_end, cigar_stride, binary_cigar, score_only, adaptive_band=adaptive_band, sides=return_sides,
                                       gap_scores=return_gap_scores)
@@ -432,15 +525,13 @@ class MicrosoftSmithWaterman:
         if cigar_stride is None:
             cigar_stride = _default_stride(max_tl, max_ql, binary_cigar)
         if out is None:
-            rec = lambda: torch.empty((n, 8), dtype=torch.int32, device=dev)  # noqa: E731
-            out = (rec(), rec() if sides else None, rec() if sides else None, torch.empty(total, dtype=torch.int32, device=dev) if gap_scores else None,
-                   None if score_only else torch.empty(n * cigar_stride, dtype=torch.uint8, device=dev),
-                   None if score_only else torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+            new = _alloc(dev)
+            out = (new((n, 8)), new((n, 8)) if sides else None, new((n, 8)) if sides else None, new(total) if gap_scores else None,
+                   None if score_only else new(n * cigar_stride, torch.uint8), None if score_only else new(n), new(n))
         aln, left, right, gs, cg, ln, st = out
         p = SWParameters(*parameters)
-        flags = ((_lib.FLAG_BINARY_CIGAR if binary_cigar else 0) | (_lib.FLAG_SCORE_ONLY if score_only else 0) |
-                 (_lib.FLAG_EXTEND_TO_QUERY_END if to_query_end else 0) | (_lib.FLAG_EXTEND_ADAPTIVE_BAND if adaptive_band else 0))
-        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        flags = _extend_flags(binary_cigar, score_only, to_query_end, adaptive_band)
+        ptr = _ptrs(dev, keep_null=True)
         rc = _lib.lib().mgl_sw_align_chain_batch_device(
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len),
             ptr(anchor_start), ptr(anchor_t), ptr(anchor_q), ptr(anchor_len), total, int(max_tl), int(max_ql), int(max_gap_tl), int(max_gap_ql),
@@ -462,19 +553,15 @@ class MicrosoftSmithWaterman:
         dev = torch.device("cuda", self._device)
         n = len(candidates)
         assert len(t_lens) == len(q_lens) == n
-        start = np.zeros(n + 1, np.int64)
-        if n:
-            np.cumsum([len(c) for c in candidates], out=start[1:])
-        flat = np.asarray([a for c in candidates for a in c], dtype=np.int32).reshape(-1, 3)
+        start, flat = _csr(candidates)
         if max_cand is None:
             max_cand = int(np.diff(start).max(initial=0))
-        g = lambda x, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dt))).to(dev)  # noqa: E731
+        g = lambda x, dt: _upload(x, dev, dt)  # noqa: E731
         out = self.chain_anchors_device(g(t_lens, np.int32), g(q_lens, np.int32), g(start, np.int64), g(flat[:, 0], np.int32), g(flat[:, 1], np.int32),
                                         g(flat[:, 2], np.int32), max_cand, max_pred, max_dist, bw, pen_gap, pen_skip, dp=return_dp)
         torch.cuda.synchronize(dev)
         cs, ct, cq, cl, score, f, pred, st = (None if x is None else x.cpu().numpy() for x in out)
-        chains = [[(int(ct[i]), int(cq[i]), int(cl[i])) for i in range(cs[k], cs[k + 1])] for k in range(n)]
-        res = ChainAnchorsResult(chains, score, st)
+        res = ChainAnchorsResult(_candidate_lists(cs, ct, cq, cl, n), score, st)
         return (res, f, pred) if return_dp else res
 
     def chain_anchors_device(self, t_len, q_len, cand_start, cand_t, cand_q, cand_len, max_cand, max_pred=64, max_dist=5000, bw=500, pen_gap=38,
@@ -489,14 +576,12 @@ class MicrosoftSmithWaterman:
         n = int(t_len.numel())
         total = int(cand_t.numel())
         dev = t_len.device
-        i32 = lambda k: torch.empty(k, dtype=torch.int32, device=dev)  # noqa: E731
         if out is None:
-            out = (torch.empty(n + 1, dtype=torch.int64, device=dev), i32(total), i32(total), i32(total), i32(n), i32(total) if dp else None,
-                   i32(total) if dp else None, i32(n))
+            new = _alloc(dev)
+            out = (new(n + 1, torch.int64), new(total), new(total), new(total), new(n), new(total) if dp else None, new(total) if dp else None, new(n))
         cs, ct, cq, cl, score, f, pred, st = out
         dist_t, dist_q = (max_dist, max_dist) if np.isscalar(max_dist) else max_dist
-        spare = torch.empty(2, dtype=torch.int64, device=dev) if n == 0 or total == 0 else None  # an empty tensor has no address: the entry wants one
-        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        ptr = _ptrs(dev)
         rc = _lib.lib().mgl_sw_chain_anchors_batch_device(
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(t_len), ptr(q_len), ptr(cand_start), ptr(cand_t), ptr(cand_q), ptr(cand_len), total,
             int(max_cand), int(max_pred), int(dist_t), int(dist_q), int(bw), int(pen_gap), int(pen_skip), ptr(cs), ptr(ct), ptr(cq), ptr(cl), ptr(score),
@@ -532,7 +617,7 @@ class MicrosoftSmithWaterman:
         out = self.seed_device(*packed[:6], k, w, max_occ, merge, max_cand)
         torch.cuda.synchronize(dev)
         cs, ct, cq, cl, st = (x.cpu().numpy() for x in out)
-        return SeedResult([[(int(ct[i]), int(cq[i]), int(cl[i])) for i in range(cs[p], cs[p + 1])] for p in range(n)], st)
+        return SeedResult(_candidate_lists(cs, ct, cq, cl, n), st)
 
     def seed_device(self, targets, t_start, t_len, queries, q_start, q_len, k=15, w=10, max_occ=8, merge=True, max_cand=4096, cand_capacity=None,
                     out=None):
@@ -549,12 +634,11 @@ class MicrosoftSmithWaterman:
         if cand_capacity is None:
             cand_capacity = int(out[1].numel()) if out is not None else min(n * int(max_cand), 1 << 30)
         if out is None:
-            i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
-            out = (torch.empty(n + 1, dtype=torch.int64, device=dev), i32(cand_capacity), i32(cand_capacity), i32(cand_capacity), i32(n))
+            new = _alloc(dev)
+            out = (new(n + 1, torch.int64), new(cand_capacity), new(cand_capacity), new(cand_capacity), new(n))
         cs, ct, cq, cl, st = out
         assert min(ct.numel(), cq.numel(), cl.numel()) >= cand_capacity and cs.numel() >= n + 1
-        spare = torch.empty(2, dtype=torch.int64, device=dev) if n == 0 or cand_capacity == 0 else None  # an empty tensor has no address: the entry wants one
-        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        ptr = _ptrs(dev)
         rc = _lib.lib().mgl_sw_seed_batch_device(
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len), int(k),
             int(w), int(max_occ), int(merge), int(max_cand), int(cand_capacity), ptr(cs), ptr(ct), ptr(cq), ptr(cl), ptr(st))
@@ -585,7 +669,7 @@ class MicrosoftSmithWaterman:
         out = self.seed_strands_device(*packed[:6], k, w, max_occ, merge, max_cand)
         torch.cuda.synchronize(dev)
         cs, ct, cq, cl, _, _, st = (x.cpu().numpy() for x in out)
-        return SeedResult([[(int(ct[i]), int(cq[i]), int(cl[i])) for i in range(cs[r], cs[r + 1])] for r in range(2 * n)], st)
+        return SeedResult(_candidate_lists(cs, ct, cq, cl, 2 * n), st)
 
     def seed_strands_device(self, targets, t_start, t_len, queries, q_start, q_len, k=15, w=10, max_occ=8, merge=True, max_cand=4096,
                             cand_capacity=None, out=None):
@@ -601,15 +685,8 @@ class MicrosoftSmithWaterman:
         dev = targets.device
         if cand_capacity is None:
             cand_capacity = int(out[1].numel()) if out is not None else min(2 * n * int(max_cand), 1 << 30)
-        if out is None:
-            i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
-            out = (torch.empty(2 * n + 1, dtype=torch.int64, device=dev), i32(cand_capacity), i32(cand_capacity), i32(cand_capacity), i32(2 * n),
-                   i32(2 * n), i32(2 * n))
-        cs, ct, cq, cl, rt, rq, st = out
-        assert min(ct.numel(), cq.numel(), cl.numel()) >= cand_capacity and cs.numel() >= 2 * n + 1
-        assert all(x is None or x.numel() >= 2 * n for x in (rt, rq, st))
-        spare = torch.empty(2, dtype=torch.int64, device=dev) if n == 0 or cand_capacity == 0 else None  # an empty tensor has no address: the entry wants one
-        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        cs, ct, cq, cl, rt, rq, st = out = _seed_rows(out, 2 * n, cand_capacity, dev)
+        ptr = _ptrs(dev)
         rc = _lib.lib().mgl_sw_seed_strands_batch_device(
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len), int(k),
             int(w), int(max_occ), int(merge), int(max_cand), int(cand_capacity), ptr(cs), ptr(ct), ptr(cq), ptr(cl), ptr(rt), ptr(rq), ptr(st))
@@ -630,13 +707,12 @@ class MicrosoftSmithWaterman:
         total = int(chain_t.numel())
         dev = queries.device
         if out is None:
-            i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
-            out = (i32(n), torch.empty_like(queries), torch.empty(n + 1, dtype=torch.int64, device=dev), i32(total), i32(total), i32(total), i32(n), i32(n))
+            new = _alloc(dev)
+            out = (new(n), torch.empty_like(queries), new(n + 1, torch.int64), new(total), new(total), new(total), new(n), new(n))
         strand, qo, as_, at, aq, al, score, st = out
         assert chain_start.numel() >= 2 * n + 1 and chain_score.numel() >= 2 * n and min(chain_q.numel(), chain_len.numel()) >= total
         assert qo.numel() >= queries.numel() and as_.numel() >= n + 1 and min(at.numel(), aq.numel(), al.numel()) >= total and strand.numel() >= n
-        spare = torch.empty(2, dtype=torch.int64, device=dev)  # an empty tensor has no address: the entry wants one
-        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        ptr = _ptrs(dev)
         rc = _lib.lib().mgl_sw_select_strand_batch_device(
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(queries), ptr(q_start), ptr(q_len), ptr(chain_start), ptr(chain_t), ptr(chain_q),
             ptr(chain_len), ptr(chain_score), total, int(queries.numel()), ptr(strand), ptr(qo), ptr(as_), ptr(at), ptr(aq), ptr(al), ptr(score), ptr(st))
@@ -687,12 +763,11 @@ class MicrosoftSmithWaterman:
         import torch
 
         dev = torch.device("cuda", self._device)
-        qs = [bytes(q) for q in queries]
-        n, packed, _ = _pack_pairs(qs, qs, dev, 16, False)
-        out = self.seed_index_device(index, *packed[3:6], strands, max_occ, max_occ_ref, merge, max_cand)
+        n, packed, _ = _pack_reads(queries, dev)
+        out = self.seed_index_device(index, *packed, strands, max_occ, max_occ_ref, merge, max_cand)
         torch.cuda.synchronize(dev)
         cs, ct, cq, cl, _, _, st = (x.cpu().numpy() for x in out)
-        return SeedResult([[(int(ct[i]), int(cq[i]), int(cl[i])) for i in range(cs[r], cs[r + 1])] for r in range(strands * n)], st)
+        return SeedResult(_candidate_lists(cs, ct, cq, cl, strands * n), st)
 
     def seed_index_device(self, index, queries, q_start, q_len, strands=2, max_occ=8, max_occ_ref=64, merge=True, max_cand=4096, cand_capacity=None,
                           out=None):
@@ -707,15 +782,8 @@ class MicrosoftSmithWaterman:
         dev = queries.device
         if cand_capacity is None:
             cand_capacity = int(out[1].numel()) if out is not None else min(rows * int(max_cand), 1 << 30)
-        if out is None:
-            i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
-            out = (torch.empty(rows + 1, dtype=torch.int64, device=dev), i32(cand_capacity), i32(cand_capacity), i32(cand_capacity), i32(rows), i32(rows),
-                   i32(rows))
-        cs, ct, cq, cl, rt, rq, st = out
-        assert min(ct.numel(), cq.numel(), cl.numel()) >= cand_capacity and cs.numel() >= rows + 1
-        assert all(x is None or x.numel() >= rows for x in (rt, rq, st))
-        spare = torch.empty(2, dtype=torch.int64, device=dev) if n == 0 or cand_capacity == 0 else None  # an empty tensor has no address: the entry wants one
-        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        cs, ct, cq, cl, rt, rq, st = out = _seed_rows(out, rows, cand_capacity, dev)
+        ptr = _ptrs(dev)
         rc = _lib.lib().mgl_sw_seed_index_batch_device(
             ctx, torch.cuda.current_stream(dev).cuda_stream, index.handle, n, ptr(queries), ptr(q_start), ptr(q_len), int(strands), int(max_occ),
             int(max_occ_ref), int(merge), int(max_cand), int(cand_capacity), ptr(cs), ptr(ct), ptr(cq), ptr(cl), ptr(rt), ptr(rq), ptr(st))
@@ -737,12 +805,11 @@ class MicrosoftSmithWaterman:
         total = int(anchor_t.numel())
         dev = q_len.device
         if out is None:
-            out = (torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
-                   anchor_t if in_place else torch.empty(total, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+            new = _alloc(dev)
+            out = (new(n, torch.int64), new(n), anchor_t if in_place else new(total), new(n))
         ts, tl, at, st = out
         assert anchor_start.numel() >= n + 1 and min(anchor_q.numel(), anchor_len.numel(), at.numel()) >= total and min(ts.numel(), tl.numel()) >= n
-        spare = torch.empty(2, dtype=torch.int64, device=dev)  # an empty tensor has no address: the entry wants one
-        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        ptr = _ptrs(dev)
         rc = _lib.lib().mgl_sw_locate_window_batch_device(
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ref_len, ptr(q_len), ptr(anchor_start), ptr(anchor_t), ptr(anchor_q), ptr(anchor_len), total,
             int(slack), int(max_tl), ptr(ts), ptr(tl), ptr(at), ptr(st))
@@ -779,22 +846,11 @@ class MicrosoftSmithWaterman:
         import torch
 
         dev = torch.device("cuda", self._device)
-        qs = [bytes(q) for q in reads]
-        n, packed, _ = _pack_pairs(qs, qs, dev, 16, False)
-        max_ql = packed[7]
-        if max_tl is None:
-            max_tl = max_ql + max_ql // 2 + 2 * int(slack)
-        stride = stages.pop("cigar_stride", None) or _default_stride(max_tl, max_ql, False)
-        _, _, chosen, window, aln = self.map_reads_device(index, *packed[3:6], max_tl, max_ql, band, zdrop, parameters, slack, strands, cigar_stride=stride,
+        n, packed, max_tl, max_ql, stride = _map_setup(reads, dev, slack, max_tl, stages)
+        _, _, chosen, window, aln = self.map_reads_device(index, *packed, max_tl, max_ql, band, zdrop, parameters, slack, strands, cigar_stride=stride,
                                                           **stages)
         torch.cuda.synchronize(dev)
-        rec, cg, ln, st = aln[0].cpu().numpy(), aln[4].cpu().numpy().reshape(n, stride), aln[5].cpu().numpy(), aln[6].cpu().numpy()
-        t_start, wst = window[0].cpu().numpy(), window[3].cpu().numpy()
-        ok = st == 0
-        strand = chosen[0].cpu().numpy() if chosen is not None else np.zeros(n, np.int32)
-        ln = np.where(ok, ln, 0).astype(np.int32)
-        return MapResult(np.where(ok, t_start + rec[:, 1], 0), np.where(ok, t_start + rec[:, 2], 0), np.where(ok, strand, 0).astype(np.int32),
-                         np.where(ok, rec[:, 0], 0).astype(np.int32), CigarColumn(cg, ln), np.where(wst != 0, wst, st).astype(np.int32))
+        return MapResult(*_map_fields(n, stride, chosen, window, aln)[0])
 
     def rank_chains(self, row_q_lens, candidates, f, pred, row_status=None, strands=2, max_chains=4, min_score=40, min_cnt=3, mask_level=128,
                     max_cand=None, return_anchors=False):
@@ -808,14 +864,11 @@ class MicrosoftSmithWaterman:
         dev = torch.device("cuda", self._device)
         rows = len(candidates)
         assert len(row_q_lens) == len(f) == len(pred) == rows and strands in (1, 2) and rows % strands == 0
-        start = np.zeros(rows + 1, np.int64)
-        if rows:
-            np.cumsum([len(c) for c in candidates], out=start[1:])
-        flat = np.asarray([a for c in candidates for a in c], dtype=np.int32).reshape(-1, 3)
+        start, flat = _csr(candidates)
         cat = lambda xs: np.asarray([v for x in xs for v in x], dtype=np.int32)  # noqa: E731
         if max_cand is None:
             max_cand = int(np.diff(start).max(initial=0))
-        g = lambda x, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=dt))).to(dev)  # noqa: E731
+        g = lambda x, dt: _upload(x, dev, dt)  # noqa: E731
         out = self.rank_chains_device(g(row_q_lens, np.int32), g(start, np.int64), g(flat[:, 0], np.int32), g(flat[:, 1], np.int32), g(flat[:, 2], np.int32),
                                       g(cat(f), np.int32), g(cat(pred), np.int32), None if row_status is None else g(row_status, np.int32), strands, max_cand,
                                       max_chains, min_score, min_cnt, mask_level, anchors=return_anchors)
@@ -824,13 +877,8 @@ class MicrosoftSmithWaterman:
         chains = [[RankedChain(*(int(v) for v in rec[p, c])) for c in range(nc[p])] for p in range(rows // strands)]
         if not return_anchors:
             return chains, st
-        anchors = []
-        for p, cs in enumerate(chains):
-            at, per = int(rs[p]), []
-            for c in cs:
-                per.append([(int(rt[i]), int(rq[i]), int(rl[i])) for i in range(at, at + c.n_anchors)])
-                at += c.n_anchors
-            anchors.append(per)
+        # a read's chains stand one behind the other from ranked_start[p] on
+        anchors = [_candidate_lists(int(rs[p]) + np.cumsum([0] + [c.n_anchors for c in cs]), rt, rq, rl, len(cs)) for p, cs in enumerate(chains)]
         return chains, anchors, st
 
     def rank_chains_device(self, row_q_len, cand_start, cand_t, cand_q, cand_len, f, pred, row_status=None, strands=2, max_cand=4096, max_chains=4,
@@ -848,14 +896,13 @@ class MicrosoftSmithWaterman:
         total = int(cand_t.numel())
         dev = row_q_len.device
         if out is None:
-            i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
-            out = (i32(n), torch.empty((n, max(int(max_chains), 0), 12), dtype=torch.int32, device=dev),
-                   torch.empty(n + 1, dtype=torch.int64, device=dev) if anchors else None, *((i32(total) if anchors else None) for _ in range(3)), i32(n))
+            new = _alloc(dev)
+            out = (new(n), new((n, max(int(max_chains), 0), 12)), new(n + 1, torch.int64) if anchors else None,
+                   *((new(total) if anchors else None) for _ in range(3)), new(n))
         nc, rec, rs, rt, rq, rl, st = out
         assert strands not in (1, 2) or (rows % strands == 0 and cand_start.numel() >= rows + 1)
         assert nc.numel() >= n and rec.numel() >= n * max_chains * 12 and min(cand_q.numel(), cand_len.numel(), f.numel(), pred.numel()) >= total
-        spare = torch.empty(2, dtype=torch.int64, device=dev)  # an empty tensor has no address: the entry wants one
-        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        ptr = _ptrs(dev)
         rc = _lib.lib().mgl_sw_rank_chains_batch_device(
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, int(strands), ptr(row_q_len), ptr(cand_start), ptr(cand_t), ptr(cand_q), ptr(cand_len), total,
             ptr(f), ptr(pred), ptr(row_status), int(max_cand), int(max_chains), int(min_score), int(min_cnt), int(mask_level), ptr(nc), ptr(rec), ptr(rs),
@@ -878,8 +925,8 @@ class MicrosoftSmithWaterman:
         if chain_out is None:  # the chain stage's tuple with f and pred in it: sized as map_reads_device sizes the seed stage's
             rows = max(int(strands), 0) * n
             total = int(seed_out[1].numel()) if seed_out is not None else cand_capacity if cand_capacity is not None else min(rows * int(max_cand), 1 << 30)
-            i32 = lambda m: torch.empty(m, dtype=torch.int32, device=dev)  # noqa: E731
-            chain_out = (torch.empty(rows + 1, dtype=torch.int64, device=dev), i32(total), i32(total), i32(total), i32(rows), i32(total), i32(total), i32(rows))
+            new = _alloc(dev)
+            chain_out = (new(rows + 1, torch.int64), new(total), new(total), new(total), new(rows), new(total), new(total), new(rows))
         assert chain_out[5] is not None and chain_out[6] is not None, "chain_out needs f and pred (chain_anchors_device(dp=True))"
         seeds, chain, chosen, window, aln = self.map_reads_device(index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters, strands=strands,
                                                                   max_cand=max_cand, cand_capacity=cand_capacity, seed_out=seed_out, chain_out=chain_out,
@@ -897,26 +944,11 @@ class MicrosoftSmithWaterman:
         import torch
 
         dev = torch.device("cuda", self._device)
-        qs = [bytes(q) for q in reads]
-        n, packed, _ = _pack_pairs(qs, qs, dev, 16, False)
-        max_ql = packed[7]
-        if max_tl is None:
-            max_tl = max_ql + max_ql // 2 + 2 * int(slack)
-        stride = stages.pop("cigar_stride", None) or _default_stride(max_tl, max_ql, False)
-        _, _, chosen, window, aln, ranked = self.map_reads_ranked_device(index, *packed[3:6], max_tl, max_ql, band, zdrop, parameters, strands=strands,
+        n, packed, max_tl, max_ql, stride = _map_setup(reads, dev, slack, max_tl, stages)
+        _, _, chosen, window, aln, ranked = self.map_reads_ranked_device(index, *packed, max_tl, max_ql, band, zdrop, parameters, strands=strands,
                                                                          slack=slack, cigar_stride=stride, **stages)
         torch.cuda.synchronize(dev)
-        rec, cg, ln, st = aln[0].cpu().numpy(), aln[4].cpu().numpy().reshape(n, stride), aln[5].cpu().numpy(), aln[6].cpu().numpy()
-        t_start, wst = window[0].cpu().numpy(), window[3].cpu().numpy()
-        ok = st == 0
-        strand = chosen[0].cpu().numpy() if chosen is not None else np.zeros(n, np.int32)
-        ln = np.where(ok, ln, 0).astype(np.int32)
-        nc, rr = ranked[0].cpu().numpy(), ranked[1].cpu().numpy()
-        mapq = np.asarray([int(rr[p, 0, 10]) if nc[p] > 0 else 0 for p in range(n)], dtype=np.int32)
-        secondary = [[(int(c[3]), int(c[4]), int(c[1]), int(c[0]), int(c[7])) for c in rr[p, 1:nc[p]]] for p in range(n)]
-        return RankedMapResult(np.where(ok, t_start + rec[:, 1], 0), np.where(ok, t_start + rec[:, 2], 0), np.where(ok, strand, 0).astype(np.int32),
-                               np.where(ok, rec[:, 0], 0).astype(np.int32), CigarColumn(cg, ln), np.where(wst != 0, wst, st).astype(np.int32), mapq,
-                               nc.astype(np.int32), secondary)
+        return RankedMapResult(*_map_fields(n, stride, chosen, window, aln)[0], *_rank_fields(n, ranked))
 
     def describe_device(self, targets, t_start, t_len, queries, q_start, q_len, aln, cigar, cigar_stride, cigar_len, status_in=None, md_stride=None,
                         xcigar_stride=None, binary_cigar=False, md=True, xcigar=True, out=None):
@@ -935,12 +967,11 @@ class MicrosoftSmithWaterman:
         md_stride = int(cigar_stride if md_stride is None else md_stride)
         xcigar_stride = int(cigar_stride if xcigar_stride is None else xcigar_stride)
         if out is None:
-            u8 = lambda want, stride: torch.empty(n * max(stride, 0), dtype=torch.uint8, device=dev) if want else None  # noqa: E731
-            out = (torch.empty((n, 8), dtype=torch.int32, device=dev), u8(md, md_stride), u8(xcigar, xcigar_stride), torch.empty(n, dtype=torch.int32, device=dev))
+            new = _alloc(dev)
+            out = (new((n, 8)), new(n * max(md_stride, 0), torch.uint8) if md else None, new(n * max(xcigar_stride, 0), torch.uint8) if xcigar else None, new(n))
         stats, mdt, xct, st = out
         assert stats.numel() >= 8 * n and (mdt is None or mdt.numel() >= n * md_stride) and (xct is None or xct.numel() >= n * xcigar_stride)
-        spare = torch.empty(2, dtype=torch.int64, device=dev)  # an empty tensor has no address: the entry wants one
-        ptr = lambda x: None if x is None else (x.data_ptr() or spare.data_ptr())  # noqa: E731
+        ptr = _ptrs(dev)
         rc = _lib.lib().mgl_sw_describe_alignments_batch_device(
             ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len), ptr(aln),
             ptr(cigar), int(cigar_stride), ptr(cigar_len), ptr(status_in), ptr(stats), ptr(mdt), md_stride, ptr(xct), xcigar_stride, ptr(st),
@@ -973,7 +1004,7 @@ class MicrosoftSmithWaterman:
             spans = [(0, len(t), 0, len(q)) for t, q in zip(refs, alts)]
         rec = np.zeros((n, 8), np.int32)
         rec[:, 1:5] = np.asarray(spans, np.int32).reshape(n, 4)
-        g = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)  # noqa: E731
+        g = lambda x: _upload(x, dev)  # noqa: E731
         args = (*packed[:6], g(rec), g(slots.reshape(-1)), stride, g(np.asarray([len(r) for r in rows], np.int32)))
         sized = self.describe_device(*args, binary_cigar=binary_cigar, md=False, xcigar=False)
         need = _fetch(sized, dev, True)[0].reshape(n, 8)
@@ -1015,23 +1046,11 @@ class MicrosoftSmithWaterman:
         import torch
 
         dev = torch.device("cuda", self._device)
-        qs = [bytes(q) for q in reads]
-        n, packed, _ = _pack_pairs(qs, qs, dev, 16, False)
-        max_ql = packed[7]
-        if max_tl is None:
-            max_tl = max_ql + max_ql // 2 + 2 * int(slack)
-        stride = stages.pop("cigar_stride", None) or _default_stride(max_tl, max_ql, False)
-        _, _, chosen, window, aln, ranked, desc = self.map_reads_described_device(index, *packed[3:6], max_tl, max_ql, band, zdrop, parameters, strands=strands,
+        n, packed, max_tl, max_ql, stride = _map_setup(reads, dev, slack, max_tl, stages)
+        _, _, chosen, window, aln, ranked, desc = self.map_reads_described_device(index, *packed, max_tl, max_ql, band, zdrop, parameters, strands=strands,
                                                                                   slack=slack, cigar_stride=stride, xcigar=bool(extended), **stages)
         torch.cuda.synchronize(dev)
-        rec, cg, ln, st = aln[0].cpu().numpy(), aln[4].cpu().numpy().reshape(n, stride), aln[5].cpu().numpy(), aln[6].cpu().numpy()
-        t_start, wst = window[0].cpu().numpy(), window[3].cpu().numpy()
-        ok = st == 0
-        strand = chosen[0].cpu().numpy() if chosen is not None else np.zeros(n, np.int32)
-        ln = np.where(ok, ln, 0).astype(np.int32)
-        nc, rr = ranked[0].cpu().numpy(), ranked[1].cpu().numpy()
-        mapq = np.asarray([int(rr[p, 0, 10]) if nc[p] > 0 else 0 for p in range(n)], dtype=np.int32)
-        secondary = [[(int(c[3]), int(c[4]), int(c[1]), int(c[0]), int(c[7])) for c in rr[p, 1:nc[p]]] for p in range(n)]
+        fields, ok, rec = _map_fields(n, stride, chosen, window, aln)
         stats, dst = desc[0].cpu().numpy().reshape(n, 8), desc[3].cpu().numpy()
         over = np.flatnonzero(ok & (dst != 0))
         if over.size:  # the alignment stands and its description does not: a text beyond its stride
@@ -1040,10 +1059,8 @@ class MicrosoftSmithWaterman:
         mds = [md[p, :stats[p, 6]].tobytes() for p in range(n)]
         nm = (stats[:, 1] + stats[:, 2] + stats[:, 3]).astype(np.int32)
         z = lambda x: np.where(ok, x, 0).astype(np.int32)  # noqa: E731
-        return DescribedMapResult(np.where(ok, t_start + rec[:, 1], 0), np.where(ok, t_start + rec[:, 2], 0), z(strand), z(rec[:, 0]), CigarColumn(cg, ln),
-                                  np.where(wst != 0, wst, st).astype(np.int32), mapq, nc.astype(np.int32), secondary, z(rec[:, 3]), z(rec[:, 4]), nm,
-                                  stats[:, 0].astype(np.int32), (stats[:, 0] + nm).astype(np.int32),
-                                  mds, CigarColumn(desc[2].cpu().numpy().reshape(n, -1), stats[:, 7].astype(np.int32)) if extended else None)
+        return DescribedMapResult(*fields, *_rank_fields(n, ranked), z(rec[:, 3]), z(rec[:, 4]), nm, stats[:, 0].astype(np.int32),
+                                  (stats[:, 0] + nm).astype(np.int32), mds, CigarColumn(desc[2].cpu().numpy().reshape(n, -1), stats[:, 7].astype(np.int32)) if extended else None)
 
     def align_packed_2bit(self, target_bases, target_base_count, t_start, t_len, query_bases, query_base_count, q_start, q_len,
                           max_tl, max_ql, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,

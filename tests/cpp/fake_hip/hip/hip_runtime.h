@@ -20,7 +20,7 @@
 #define __forceinline__ inline
 
 typedef int hipError_t;
-enum { hipSuccess = 0, hipErrorOutOfMemory = 2, hipErrorInvalidValue = 1, hipErrorNoDevice = 100, hipErrorHostMemoryAlreadyRegistered = 712 };
+enum { hipSuccess = 0, hipErrorOutOfMemory = 2, hipErrorInvalidValue = 1, hipErrorNoDevice = 100, hipErrorHostMemoryAlreadyRegistered = 712, hipErrorLaunchFailure = 719 };
 typedef struct fakeStream *hipStream_t;
 typedef struct fakeEvent *hipEvent_t;
 enum hipMemcpyKind { hipMemcpyHostToHost = 0, hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3 };

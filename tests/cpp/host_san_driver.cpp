@@ -8,6 +8,8 @@
 //   * mgl_sw_align_batch_multi over two (fake) devices: shard boundaries, one host thread per device
 //   * 48 threads through mgl_sw_align (the coalescing front-end): parking, batching, wake-up by shard, the caller whose
 //     buffer is too small (CIGAR_OVERFLOW) and the pair whose walk fails on the "device" (status handed back verbatim)
+//   * the frame of a stage entry (mgl_amd/csrc/sw_stage_host.h) driven directly: the refusal, the null context, a failed launch behind
+//     a borrowed workspace, a stage without a kernel id (the timing record keeps its fill_kernel, and a running sum its launches)
 // Every answer is compared with the CPU checker called directly.
 #include <algorithm>
 #include <atomic>
@@ -21,6 +23,7 @@
 #include <vector>
 
 #include "../../include/mgl_sw.h"
+#include "../../mgl_amd/csrc/sw_stage_host.h"
 #include "../../oracle/sw_oracle.h"
 
 int *fake_hip_current_device(void); // tests/cpp/fake_device.cpp: the calling thread's current HIP device
@@ -466,6 +469,92 @@ int main()
                                       11, MGL_SW_OS_SOFTCLIP, off1, nullptr, cg1, 64, len1, nullptr, 0) == MGL_SW_ERR_BAD_ARG);
     }
     mgl_sw_ctx_destroy(ctx);
+
+    // ---- the frame of a stage entry (sw_stage_host.h) on a context of its own, around ordinary batches of 512 of the uniform pairs
+    {
+        using namespace mgl_sw_host;
+        Batch few;
+        for (int64_t k = 0; k < 512; ++k)
+            few.add(std::string(uni.t.begin() + uni.toff[(size_t)k], uni.t.begin() + uni.toff[(size_t)k + 1]),
+                    std::string(uni.q.begin() + uni.qoff[(size_t)k], uni.q.begin() + uni.qoff[(size_t)k + 1]));
+        const Expect ef = expect(few, MGL_SW_OS_INDEL);
+        mgl_sw_ctx *sc_ctx = nullptr;
+        CHECK(mgl_sw_ctx_create(0, &sc_ctx) == 0 && mgl_sw_ctx_set_small_kernel(sc_ctx, 1) == 0 && mgl_sw_ctx_set_lane_kernel(sc_ctx, 2) == 0);
+        const int64_t n = few.n();
+        auto batch = [&] { // an ordinary batch, compared with the checker
+            std::vector<int32_t> off((size_t)n, -9), len((size_t)n);
+            std::vector<mgl_sw_score> sc((size_t)n);
+            std::vector<char> cg((size_t)n * 64, 1);
+            CHECK(mgl_sw_align_batch(sc_ctx, n, few.t.data(), few.toff.data(), few.q.data(), few.qoff.data(), 200, -150, 260, 11, MGL_SW_OS_INDEL, off.data(),
+                                     sc.data(), cg.data(), 64, len.data()) == 0);
+            compare(few, ef, off, sc, cg, 64, len, nullptr);
+        };
+        mgl_sw_timing tm;
+        // refuse: the text is "<entry>: <bad>" and nothing else; without a context nothing is touched
+        batch();
+        CHECK(refuse(sc_ctx, "mgl_sw_some_entry", "n < 0") == MGL_SW_ERR_BAD_ARG);
+        CHECK(std::string(mgl_sw_last_error(sc_ctx)) == "mgl_sw_some_entry: n < 0");
+        CHECK(refuse(nullptr, "mgl_sw_some_entry", "n < 0") == MGL_SW_ERR_BAD_ARG);
+        CHECK(std::string(mgl_sw_last_error(sc_ctx)) == "mgl_sw_some_entry: n < 0");
+        // a well-formed call without a context: there are (fake) devices, so it is the argument that is bad
+        CHECK(no_context() == MGL_SW_ERR_BAD_ARG);
+        CHECK(workspace_limit(sc_ctx) % 256 == 0 && workspace_limit(sc_ctx) >= 256);
+        // a launch that fails behind a borrowed workspace: ctx_hip_fail's status and text, and the workspace is back -- the next batch runs
+        {
+            Stage stage(sc_ctx, nullptr);
+            unsigned char *ws = nullptr;
+            CHECK(stage.borrow(4096, &ws) == MGL_SW_OK && ws != nullptr);
+            memset(ws, 0x5a, 4096);
+            CHECK(stage.fail(hipErrorLaunchFailure, "launch_x") == MGL_SW_ERR_DEVICE);
+            CHECK(stage.done() == MGL_SW_OK); // (nothing is borrowed any more: nothing to do)
+        }
+        CHECK(std::string(mgl_sw_last_error(sc_ctx)) == std::string("launch_x: ") + hipGetErrorString(hipErrorLaunchFailure));
+        batch();
+        CHECK(mgl_sw_ctx_get_timing(sc_ctx, &tm) == 0 && tm.fill_kernel == MGL_SW_KERNEL_LANE16_CK && tm.dp_launches >= 1);
+        const int per_batch = tm.dp_launches;
+        // a stage without a kernel id, default mode: the record is reset and keeps the batch's fill_kernel
+        {
+            Stage stage(sc_ctx, nullptr);
+            unsigned char *ws = nullptr;
+            CHECK(stage.limit() == workspace_limit(sc_ctx) && stage.borrow(256, &ws) == MGL_SW_OK);
+            CHECK(stage.done(kKeepFillKernel, 0) == MGL_SW_OK);
+        }
+        CHECK(mgl_sw_ctx_get_timing(sc_ctx, &tm) == 0 && tm.fill_kernel == MGL_SW_KERNEL_LANE16_CK && tm.dp_launches == 0);
+        // a stage with a kernel id and counted launches, for contrast
+        {
+            Stage stage(sc_ctx, nullptr);
+            unsigned char *ws = nullptr;
+            CHECK(stage.borrow(256, &ws) == MGL_SW_OK);
+            stage.kernel = MGL_SW_KERNEL_EXTEND;
+            stage.launches = 2;
+            CHECK(stage.done() == MGL_SW_OK);
+        }
+        CHECK(mgl_sw_ctx_get_timing(sc_ctx, &tm) == 0 && tm.fill_kernel == MGL_SW_KERNEL_EXTEND && tm.dp_launches == 2);
+        // no borrow: done() and fail() leave the record untouched
+        {
+            Stage stage(sc_ctx, nullptr);
+            CHECK(stage.done(MGL_SW_KERNEL_BANDED, 7) == MGL_SW_OK);
+        }
+        CHECK(mgl_sw_ctx_get_timing(sc_ctx, &tm) == 0 && tm.fill_kernel == MGL_SW_KERNEL_EXTEND && tm.dp_launches == 2);
+        {
+            Stage stage(sc_ctx, nullptr);
+            stage.kernel = MGL_SW_KERNEL_BANDED;
+            CHECK(stage.fail(hipErrorOutOfMemory, "launch_y") == MGL_SW_ERR_NOMEM);
+        }
+        CHECK(mgl_sw_ctx_get_timing(sc_ctx, &tm) == 0 && tm.fill_kernel == MGL_SW_KERNEL_EXTEND && tm.dp_launches == 2);
+        // profiling 3, a running sum: a stage without a kernel id between two batches wipes nothing
+        CHECK(mgl_sw_ctx_set_profiling(sc_ctx, 3) == 0);
+        batch();
+        {
+            Stage stage(sc_ctx, nullptr);
+            unsigned char *ws = nullptr;
+            CHECK(stage.borrow(256, &ws) == MGL_SW_OK && stage.done(kKeepFillKernel, 0) == MGL_SW_OK);
+        }
+        batch();
+        CHECK(mgl_sw_ctx_get_timing(sc_ctx, &tm) == 0 && tm.fill_kernel == MGL_SW_KERNEL_LANE16_CK && tm.dp_launches == 2 * per_batch);
+        CHECK(mgl_sw_ctx_get_timing(sc_ctx, &tm) == 0 && tm.dp_launches == 0); // (read and cleared)
+        mgl_sw_ctx_destroy(sc_ctx);
+    }
 
     // ---- several devices from one process
     {
