@@ -25,24 +25,12 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "sw_index.h"
-#include "sw_seed_dev.h"
+#include "sw_seed_sketch.h"
 
 namespace mgl_sw_dev {
 
 namespace {
 
-constexpr int INDEX_ST_BAD_ARG = 1, INDEX_ST_UNSUPPORTED = 5; // mgl_sw_status
-constexpr int INDEX_SPAN = SEED_BLOCK + 2 * SEED_MAX_W;      // positions staged for one block (B + 2 w - 2 at most)
-
-struct IndexSketchLds {
-    uint32_t key[INDEX_SPAN];
-    uint32_t hash[INDEX_SPAN];
-    uint32_t flag[SEED_BLOCK / 4]; // a byte per position of the block
-    uint8_t code[INDEX_SPAN + SEED_MAX_K];
-    uint8_t valid[INDEX_SPAN];
-    int wave_sum[SEED_THREADS / 64];
-};
-__shared__ IndexSketchLds s;              // both sketching kernels'
 __shared__ uint64_t s_tab[SEED_LDS_TAB];   // sw_seed_index_kernel's alone, and s_hits
 __shared__ uint64_t s_hits[SEED_LDS_HITS];
 struct IndexProbeLds { // a probe step, per thread: where its hits start in the step, its key's first entry, occ_I << 8 | occ_Q
@@ -52,80 +40,8 @@ struct IndexProbeLds { // a probe step, per thread: where its hits start in the 
 };
 __shared__ IndexProbeLds s_probe;
 static_assert(SEED_MAX_OCC < 256, "occ_Q shares a word with occ_I");
-static_assert(sizeof(IndexSketchLds) + sizeof(s_tab) + sizeof(s_hits) + sizeof(IndexProbeLds) <= 80 * 1024, "two workgroups share a CU's 160 KiB of LDS");
+static_assert(sizeof(SeedSketchLds) + sizeof(s_tab) + sizeof(s_hits) + sizeof(IndexProbeLds) <= 80 * 1024, "two workgroups share a CU's 160 KiB of LDS");
 static_assert(SEED_LDS_TAB * 8 >= SEED_LDS_HITS * 12, "the runs and their lengths fit where the table was");
-
-// the exclusive prefix sum of v over the workgroup, and the sum
-__device__ inline int index_block_scan(const int v, int &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) s.wave_sum[wave] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int x = 0; x < SEED_THREADS / 64; ++x) {
-        const int ws = s.wave_sum[x];
-        before += x < wave ? ws : 0;
-        all += ws;
-    }
-    __syncthreads();
-    total = all;
-    return before + incl - v;
-}
-
-// strand_sketch_block of sw_seed_strands.hip over this file's LDS.  Positions [p0, p0 + SEED_BLOCK) of the ORIENTED sequence (`rev`: the
-// reverse complement of seq, nk + k - 1 bytes, without making it): key, hash and validity of every position a window over them can
-// see, from `lo` on (returned), and flag[] set for the selected ones among them.
-__device__ __noinline__ int64_t index_sketch_block(const uint8_t *seq, const int64_t nk, const int k, const int w, const int64_t p0, const bool rev)
-{
-    const int tid = threadIdx.x;
-    const int64_t lo = p0 - w + 1 > 0 ? p0 - w + 1 : 0;
-    const int64_t hi = p0 + SEED_BLOCK + w - 2 < nk - 1 ? p0 + SEED_BLOCK + w - 2 : nk - 1; // the last position a window sees
-    const int npos = (int)(hi - lo + 1), nbytes = npos + k - 1;
-    const int64_t last = nk + k - 2; // the sequence's last byte
-    for (int i = tid; i < nbytes; i += SEED_THREADS) {
-        const uint8_t c = seed_code(seq[rev ? last - (lo + i) : lo + i]); // (lo + i <= hi + k - 1 <= last)
-        s.code[i] = rev && c < 4 ? 3 - c : c;
-    }
-    s.flag[tid] = 0;
-    __syncthreads();
-    for (int i = tid; i < npos; i += SEED_THREADS) {
-        uint32_t key = 0, bad = 0;
-        for (int j = 0; j < k; ++j) {
-            const uint32_t c = s.code[i + j];
-            bad |= c >> 2;
-            key = key << 2 | (c & 3);
-        }
-        s.key[i] = key;
-        s.hash[i] = seed_hash(key);
-        s.valid[i] = !bad;
-    }
-    __syncthreads();
-    const int64_t last_win = nk - w > 0 ? nk - w : 0;
-    const int64_t a_hi = p0 + SEED_BLOCK - 1 < last_win ? p0 + SEED_BLOCK - 1 : last_win;
-    uint8_t *const flag = reinterpret_cast<uint8_t *>(s.flag);
-    for (int64_t a = lo + tid; a <= a_hi; a += SEED_THREADS) {
-        const int from = (int)(a - lo), to = (int)((a + w < nk ? a + w : nk) - lo);
-        int best = -1;
-        uint32_t best_h = 0;
-        for (int i = from; i < to; ++i) {
-            const uint32_t h = s.hash[i];
-            const bool take = s.valid[i] && (best < 0 || h < best_h);
-            best = take ? i : best;
-            best_h = take ? h : best_h;
-        }
-        const int64_t at = best + lo - p0;
-        if (best >= 0 && at >= 0 && at < SEED_BLOCK) flag[at] = 1;
-    }
-    __syncthreads();
-    return lo;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- the build
 
@@ -137,9 +53,9 @@ __global__ __launch_bounds__(SEED_THREADS) void sw_index_sketch_kernel(const Ind
     const uint8_t *const flag = reinterpret_cast<const uint8_t *>(s.flag);
     for (int64_t b = blockIdx.x; b < a.blocks; b += gridDim.x) {
         const int64_t p0 = b * SEED_BLOCK;
-        const int64_t lo = index_sketch_block(a.ref, nk, a.k, a.w, p0, false);
+        const int64_t lo = seed_sketch_block(a.ref, nk, a.k, a.w, p0, false);
         int total;
-        const int before = index_block_scan(__popc(s.flag[tid]), total);
+        const int before = seed_block_scan(__popc(s.flag[tid]), total);
         if (pass == 0) {
             if (tid == 0) a.block_count[b] = (uint32_t)total;
         } else {
@@ -163,12 +79,7 @@ __global__ __launch_bounds__(INDEX_SCAN_THREADS) void sw_index_scan_kernel(const
     for (int64_t base = 0; base < a.blocks; base += INDEX_SCAN_THREADS) {
         const int64_t b = base + tid;
         const uint32_t own = b < a.blocks ? a.block_count[b] : 0;
-        uint32_t incl = own;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
+        const uint32_t incl = wave_inclusive_sum(own);
         if (lane == 63) wave_sum[wave] = incl;
         __syncthreads();
         uint32_t before = carry, all = 0;
@@ -234,39 +145,6 @@ __device__ inline int index_lookup(const IndexView &ix, const uint32_t key, cons
     return cnt > max_occ_ref ? 0 : cnt;
 }
 
-// (a) a row's table, sorted by (key, position), in s_tab or -- above SEED_LDS_TAB entries -- in `slot`.
-// -> its entries, or -1 for a sketch above SEED_MAX_QUERY_SEEDS
-__device__ __forceinline__ int index_build_table(const uint8_t *Q, const int nkq, const int k, const int w, const bool rev, uint64_t *slot)
-{
-    const int tid = threadIdx.x;
-    const uint8_t *const flag = reinterpret_cast<const uint8_t *>(s.flag);
-    int nq = 0;
-    for (uint32_t p0 = 0; (int64_t)p0 < nkq; p0 += SEED_BLOCK) { // (unsigned: the step past a sequence of nearly 2^31 bytes)
-        const int64_t lo = index_sketch_block(Q, nkq, k, w, p0, rev);
-        int total;
-        int at = nq + index_block_scan(__popc(s.flag[tid]), total);
-        if (nq + total > SEED_MAX_QUERY_SEEDS) return -1;
-        if (nq <= SEED_LDS_TAB && nq + total > SEED_LDS_TAB) // the table leaves LDS
-            for (int i = tid; i < nq; i += SEED_THREADS) slot[i] = s_tab[i];
-        uint64_t *const tab = nq + total > SEED_LDS_TAB ? slot : s_tab;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (flag[tid * 4 + j]) {
-                const int64_t pos = p0 + tid * 4 + j;
-                tab[at++] = (uint64_t)s.key[pos - lo] << 32 | (uint64_t)pos;
-            }
-        nq += total;
-        __syncthreads();
-    }
-    if (nq == 0) return 0;
-    uint64_t *const tab = nq > SEED_LDS_TAB ? slot : s_tab;
-    const int n2 = seed_pow2(nq);
-    for (int i = nq + tid; i < n2; i += SEED_THREADS) tab[i] = ~0ull;
-    __syncthreads();
-    seed_bitonic(tab, nullptr, n2);
-    return nq;
-}
-
 // (b) the sorted table against the index: the row's raw hits (t << 32 | q) in key order, in s_hits or -- above SEED_LDS_HITS -- in `slot`.
 // -> R, or -1 beyond max_cand
 __device__ __forceinline__ int index_probe(const IndexView &ix, const uint64_t *tab, const int nq, uint64_t *slot, const int max_occ, const int max_occ_ref,
@@ -292,7 +170,7 @@ __device__ __forceinline__ int index_probe(const IndexView &ix, const uint64_t *
             }
         }
         int total;
-        const int start = index_block_scan(mine, total); // where this thread's hits begin in the step
+        const int start = seed_block_scan(mine, total); // where this thread's hits begin in the step
         if (R + total > max_cand) return -1;
         if (R <= SEED_LDS_HITS && R + total > SEED_LDS_HITS) // the hits leave LDS (max_cand is above SEED_LDS_HITS: the slot has the room)
             for (int x = tid; x < R; x += SEED_THREADS) slot[x] = s_hits[x];
@@ -317,70 +195,6 @@ __device__ __forceinline__ int index_probe(const IndexView &ix, const uint64_t *
         __syncthreads();
     }
     return R;
-}
-
-// (c), (d) a row's R raw hits, in any order -> its candidates, ascending by (t, q), in its staging (st: t, then q, then l, max_cand each).
-// `run` and `len` hold the merged runs meanwhile.  -> N, the row's candidates
-__device__ __forceinline__ int index_stage_row(uint64_t *hits, const int R, uint64_t *run, uint32_t *len, int32_t *st, const int max_cand, const int k,
-                                               const int merge)
-{
-    const int tid = threadIdx.x;
-    int32_t *const sq = st + max_cand, *const sl = sq + max_cand;
-    if (R == 0) return 0;
-    const int n2 = seed_pow2(R);
-    if (!merge) {
-        for (int i = R + tid; i < n2; i += SEED_THREADS) hits[i] = ~0ull;
-        __syncthreads();
-        seed_bitonic(hits, nullptr, n2);
-        for (int i = tid; i < R; i += SEED_THREADS) {
-            const uint64_t h = hits[i];
-            st[i] = (int32_t)(h >> 32);
-            sq[i] = (int32_t)(uint32_t)h;
-            sl[i] = k;
-        }
-        return R;
-    }
-    // by (diagonal, t); heads and tails of the runs; back by (t, q)
-    for (int i = tid; i < n2; i += SEED_THREADS) {
-        const uint64_t h = i < R ? hits[i] : 0;
-        const uint32_t t = (uint32_t)(h >> 32), q = (uint32_t)h;
-        hits[i] = i < R ? (uint64_t)(t - q + 0x80000000u) << 32 | t : ~0ull;
-    }
-    __syncthreads();
-    seed_bitonic(hits, nullptr, n2);
-    int N = 0;
-    for (int base = 0; base < R; base += SEED_THREADS) {
-        const int i = base + tid;
-        bool head = false, tail = false;
-        uint64_t me = 0;
-        if (i < R) {
-            me = hits[i];
-            const uint64_t prev = i > 0 ? hits[i - 1] : 0, next = i + 1 < R ? hits[i + 1] : 0;
-            head = i == 0 || (prev >> 32) != (me >> 32) || me > prev + (uint64_t)k; // (the same diagonal: the difference is t's)
-            tail = i + 1 == R || (next >> 32) != (me >> 32) || next > me + (uint64_t)k;
-        }
-        int total;
-        const int r = N + index_block_scan(head ? 1 : 0, total) + (head ? 1 : 0) - 1; // the run this hit belongs to
-        const uint32_t t = (uint32_t)me, d = (uint32_t)(me >> 32);
-        if (head) run[r] = (uint64_t)t << 32 | (uint32_t)(t - d + 0x80000000u);
-        if (tail) len[r] = t + (uint32_t)k; // the run's end; its length once the head is known to all
-        N += total;
-    }
-    __syncthreads();
-    const int m2 = seed_pow2(N);
-    for (int i = tid; i < m2; i += SEED_THREADS) {
-        if (i < N) len[i] -= (uint32_t)(run[i] >> 32);
-        else run[i] = ~0ull, len[i] = 0;
-    }
-    __syncthreads();
-    seed_bitonic(run, len, m2);
-    for (int i = tid; i < N; i += SEED_THREADS) {
-        const uint64_t h = run[i];
-        st[i] = (int32_t)(h >> 32);
-        sq[i] = (int32_t)(uint32_t)h;
-        sl[i] = (int32_t)len[i];
-    }
-    return N;
 }
 
 __global__ __launch_bounds__(SEED_THREADS) void sw_seed_index_kernel(const SeedIndexArgs aa)
@@ -413,24 +227,24 @@ __global__ __launch_bounds__(SEED_THREADS) void sw_seed_index_kernel(const SeedI
                 if (a.status) a.status[row] = status;
             };
             if (ql < 1) {
-                finish(0, INDEX_ST_BAD_ARG);
+                finish(0, SEED_ST_BAD_ARG);
                 continue;
             }
             // ---- (a) nq < 0: the row is refused; nq = 0: no key to look up, no hit
-            const int nq = index_build_table(Q, ql - k + 1, k, w, r == 1, slot_tab);
+            const int nq = seed_build_table(Q, ql - k + 1, k, w, r == 1, s_tab, slot_tab, SEED_LDS_TAB);
             if (nq < 0) {
-                finish(0, INDEX_ST_UNSUPPORTED);
+                finish(0, SEED_ST_UNSUPPORTED);
                 continue;
             }
             // ---- (b)
             const int R = index_probe(aa.ix, nq > SEED_LDS_TAB ? slot_tab : s_tab, nq, slot_hits, a.max_occ, aa.max_occ_ref, a.max_cand);
             if (R < 0) {
-                finish(0, INDEX_ST_UNSUPPORTED);
+                finish(0, SEED_ST_UNSUPPORTED);
                 continue;
             }
             // ---- (c), (d) the runs go where the table was: it is not read again
             const bool in_lds = R <= SEED_LDS_HITS;
-            const int N = index_stage_row(in_lds ? s_hits : slot_hits, R, in_lds ? s_tab : slot_tab,
+            const int N = seed_stage_row<false>(in_lds ? s_hits : slot_hits, R, in_lds ? s_tab : slot_tab,
                                           in_lds ? reinterpret_cast<uint32_t *>(s_tab + SEED_LDS_HITS) : slot_len, stage + row * 3 * a.max_cand, a.max_cand,
                                           k, a.merge);
             finish(N, 0);
@@ -453,7 +267,7 @@ __global__ __launch_bounds__(64) void sw_locate_window_kernel(const LocateArgs a
             mine = mine || l < 1 || t < 0 || q < 0 || t + l > a.ref_len || q + l > ql;
         }
         bad = bad || __any(mine);
-        int status = bad ? INDEX_ST_BAD_ARG : 0;
+        int status = bad ? SEED_ST_BAD_ARG : 0;
         int64_t lo = 0, hi = 0;
         if (!bad && K > 0) { // (the first and the last anchor are read before any is rebased: the output may be the input)
             const int64_t t0 = a.anchor_t[a0], q0 = a.anchor_q[a0];
@@ -462,7 +276,7 @@ __global__ __launch_bounds__(64) void sw_locate_window_kernel(const LocateArgs a
             lo = lo > 0 ? lo : 0;
             hi = tK + lK + (ql - qK - lK) + a.slack;
             hi = hi < a.ref_len ? hi : a.ref_len;
-            if (hi - lo > a.max_tl) status = INDEX_ST_UNSUPPORTED;
+            if (hi - lo > a.max_tl) status = SEED_ST_UNSUPPORTED;
         }
         const bool kept = status == 0 && K > 0;
         if (kept)

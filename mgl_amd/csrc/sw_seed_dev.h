@@ -1,5 +1,6 @@
-// sw_seed_dev.h -- the device helpers that sw_seed.hip and sw_seed_strands.hip share: the k-mer's code and hash, and the bitonic sort of a
-// workgroup of SEED_THREADS.  None of them names a kernel's LDS; each translation unit gets its own copy (unnamed namespace).
+// sw_seed_dev.h -- the device helpers that the seeding kernels and sw_rank.hip share: the k-mer's code and hash, and the bitonic sort of a
+// workgroup of SEED_THREADS.  None of them names LDS (what does is sw_seed_sketch.h's); each translation unit gets its own copy (unnamed
+// namespace).
 #ifndef MGL_SW_SEED_DEV_H
 #define MGL_SW_SEED_DEV_H
 

@@ -19,238 +19,17 @@
 // sw_select_strand_kernel (a thread per pair: the checks, the strand, K_p), sw_select_strand_scan_kernel (one block, the prefix sum of
 // K_p with a running carry, 1024 pairs a step) and sw_select_strand_pack_kernel (a wave per pair: the chosen row's anchors and the
 // oriented read, in 4-byte stores between the unaligned ends).
-#include "sw_seed_dev.h"
+#include "sw_seed_sketch.h"
 #include "sw_seed_strands.h"
 
 namespace mgl_sw_dev {
 
 namespace {
 
-constexpr int STRAND_ST_BAD_ARG = 1, STRAND_ST_UNSUPPORTED = 5; // mgl_sw_status
-constexpr int STRAND_SPAN = SEED_BLOCK + 2 * SEED_MAX_W;        // positions staged for one block (B + 2 w - 2 at most)
-
-struct StrandLds {
-    uint64_t tab[2][STRAND_LDS_TAB];   // by orientation; (c) reuses both as one area
-    uint64_t hits[2][STRAND_LDS_HITS]; // by row
-    uint32_t key[STRAND_SPAN];
-    uint32_t hash[STRAND_SPAN];
-    uint32_t flag[SEED_BLOCK / 4]; // a byte per position of the block
-    uint8_t code[STRAND_SPAN + SEED_MAX_K];
-    uint8_t valid[STRAND_SPAN];
-    int wave_sum[SEED_THREADS / 64];
-};
-static_assert(sizeof(StrandLds) <= 80 * 1024, "two workgroups share a CU's 160 KiB of LDS");
+__shared__ uint64_t s_tab[2][STRAND_LDS_TAB];   // sw_seed_strands_kernel's alone, and s_hits.  By orientation; (c) reuses both as one area
+__shared__ uint64_t s_hits[2][STRAND_LDS_HITS]; // by row
+static_assert(sizeof(SeedSketchLds) + sizeof(s_tab) + sizeof(s_hits) <= 80 * 1024, "two workgroups share a CU's 160 KiB of LDS");
 static_assert(2 * STRAND_LDS_TAB * 8 >= STRAND_LDS_HITS * 12, "the runs and their lengths fit where the two tables were");
-__shared__ StrandLds s; // sw_seed_strands_kernel's alone
-
-// the exclusive prefix sum of v over the workgroup, and the sum
-__device__ inline int strand_block_scan(const int v, int &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) s.wave_sum[wave] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int x = 0; x < SEED_THREADS / 64; ++x) {
-        const int ws = s.wave_sum[x];
-        before += x < wave ? ws : 0;
-        all += ws;
-    }
-    __syncthreads();
-    total = all;
-    return before + incl - v;
-}
-
-// seed_sketch_block of sw_seed.hip with one more argument: `rev` sketches the reverse complement of seq (nk + k - 1 bytes) without
-// making it.  Positions [p0, p0 + SEED_BLOCK) of the ORIENTED sequence: key, hash and validity of every position a window over them can
-// see, from `lo` on (returned), and flag[] set for the selected ones among them.
-__device__ __noinline__ int64_t strand_sketch_block(const uint8_t *seq, const int64_t nk, const int k, const int w, const int64_t p0, const bool rev)
-{
-    const int tid = threadIdx.x;
-    const int64_t lo = p0 - w + 1 > 0 ? p0 - w + 1 : 0;
-    const int64_t hi = p0 + SEED_BLOCK + w - 2 < nk - 1 ? p0 + SEED_BLOCK + w - 2 : nk - 1; // the last position a window sees
-    const int npos = (int)(hi - lo + 1), nbytes = npos + k - 1;
-    const int64_t last = nk + k - 2; // the sequence's last byte
-    for (int i = tid; i < nbytes; i += SEED_THREADS) {
-        const uint8_t c = seed_code(seq[rev ? last - (lo + i) : lo + i]); // (lo + i <= hi + k - 1 <= last)
-        s.code[i] = rev && c < 4 ? 3 - c : c;
-    }
-    s.flag[tid] = 0;
-    __syncthreads();
-    for (int i = tid; i < npos; i += SEED_THREADS) {
-        uint32_t key = 0, bad = 0;
-        for (int j = 0; j < k; ++j) {
-            const uint32_t c = s.code[i + j];
-            bad |= c >> 2;
-            key = key << 2 | (c & 3);
-        }
-        s.key[i] = key;
-        s.hash[i] = seed_hash(key);
-        s.valid[i] = !bad;
-    }
-    __syncthreads();
-    const int64_t last_win = nk - w > 0 ? nk - w : 0;
-    const int64_t a_hi = p0 + SEED_BLOCK - 1 < last_win ? p0 + SEED_BLOCK - 1 : last_win;
-    uint8_t *const flag = reinterpret_cast<uint8_t *>(s.flag);
-    for (int64_t a = lo + tid; a <= a_hi; a += SEED_THREADS) {
-        const int from = (int)(a - lo), to = (int)((a + w < nk ? a + w : nk) - lo);
-        int best = -1;
-        uint32_t best_h = 0;
-        for (int i = from; i < to; ++i) {
-            const uint32_t h = s.hash[i];
-            const bool take = s.valid[i] && (best < 0 || h < best_h);
-            best = take ? i : best;
-            best_h = take ? h : best_h;
-        }
-        const int64_t at = best + lo - p0;
-        if (best >= 0 && at >= 0 && at < SEED_BLOCK) flag[at] = 1;
-    }
-    __syncthreads();
-    return lo;
-}
-
-// (a) one orientation's table, sorted by (key, position), in `lds` or -- above STRAND_LDS_TAB entries -- in `slot`.
-// -> its entries, or -1 for a sketch above SEED_MAX_QUERY_SEEDS
-__device__ __forceinline__ int strand_build_table(const uint8_t *Q, const int nkq, const int k, const int w, const bool rev, uint64_t *lds, uint64_t *slot)
-{
-    const int tid = threadIdx.x;
-    const uint8_t *const flag = reinterpret_cast<const uint8_t *>(s.flag);
-    int nq = 0;
-    for (uint32_t p0 = 0; (int64_t)p0 < nkq; p0 += SEED_BLOCK) { // (unsigned: the step past a sequence of nearly 2^31 bytes)
-        const int64_t lo = strand_sketch_block(Q, nkq, k, w, p0, rev);
-        const uint32_t f = s.flag[tid];
-        int total;
-        int at = nq + strand_block_scan(__popc(f), total);
-        if (nq + total > SEED_MAX_QUERY_SEEDS) return -1;
-        if (nq <= STRAND_LDS_TAB && nq + total > STRAND_LDS_TAB) // the table leaves LDS
-            for (int i = tid; i < nq; i += SEED_THREADS) slot[i] = lds[i];
-        uint64_t *const tab = nq + total > STRAND_LDS_TAB ? slot : lds;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (flag[tid * 4 + j]) {
-                const int64_t pos = p0 + tid * 4 + j;
-                tab[at++] = (uint64_t)s.key[pos - lo] << 32 | (uint64_t)pos;
-            }
-        nq += total;
-        __syncthreads();
-    }
-    if (nq == 0) return 0;
-    uint64_t *const tab = nq > STRAND_LDS_TAB ? slot : lds;
-    const int n2 = seed_pow2(nq);
-    for (int i = nq + tid; i < n2; i += SEED_THREADS) tab[i] = ~0ull;
-    __syncthreads();
-    seed_bitonic(tab, nullptr, n2);
-    return nq;
-}
-
-// (b) the window's block that strand_sketch_block left in LDS (positions from p0, staged from lo) against one table: the row's raw hits
-// (t << 32 | q) behind the R it has, ascending.  -> the new R, or -1 beyond max_cand
-__device__ __noinline__ int strand_probe_block(const uint64_t *tab, const int nq, uint64_t *lds, uint64_t *slot, const int R, const uint32_t p0,
-                                               const int64_t lo, const int max_occ, const int max_cand)
-{
-    const int tid = threadIdx.x;
-    const uint8_t *const flag = reinterpret_cast<const uint8_t *>(s.flag);
-    int first[4], cnt[4], sum = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        first[j] = cnt[j] = 0;
-        if (flag[tid * 4 + j]) {
-            const uint32_t key = s.key[p0 + tid * 4 + j - lo];
-            const uint64_t want = (uint64_t)key << 32;
-            int b = 0, e = nq; // the first entry not below `want`
-            while (b < e) {
-                const int m = (b + e) >> 1;
-                if (tab[m] < want) b = m + 1;
-                else e = m;
-            }
-            int c = 0;
-            while (b + c < nq && c <= max_occ && (uint32_t)(tab[b + c] >> 32) == key) ++c;
-            first[j] = b;
-            cnt[j] = c <= max_occ ? c : 0;
-            sum += cnt[j];
-        }
-    }
-    int total;
-    int at = R + strand_block_scan(sum, total);
-    if (R + total > max_cand) return -1;
-    if (R <= STRAND_LDS_HITS && R + total > STRAND_LDS_HITS) // the hits leave LDS (max_cand is above STRAND_LDS_HITS: the slot has the room)
-        for (int i = tid; i < R; i += SEED_THREADS) slot[i] = lds[i];
-    uint64_t *const hits = R + total > STRAND_LDS_HITS ? slot : lds;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const uint64_t t = (uint64_t)(p0 + tid * 4 + j) << 32;
-        for (int c = 0; c < cnt[j]; ++c) hits[at++] = t | (uint32_t)tab[first[j] + c];
-    }
-    __syncthreads();
-    return R + total;
-}
-
-// (c), (d) a row's R raw hits -> its candidates in its staging (st: t, then q, then l, max_cand each).  `run` and `len` hold the merged
-// runs meanwhile.  -> N, the row's candidates
-__device__ __forceinline__ int strand_stage_row(uint64_t *hits, const int R, uint64_t *run, uint32_t *len, int32_t *st, const int max_cand, const int k,
-                                             const int merge)
-{
-    const int tid = threadIdx.x;
-    int32_t *const sq = st + max_cand, *const sl = sq + max_cand;
-    if (!merge || R == 0) {
-        for (int i = tid; i < R; i += SEED_THREADS) {
-            const uint64_t h = hits[i];
-            st[i] = (int32_t)(h >> 32);
-            sq[i] = (int32_t)(uint32_t)h;
-            sl[i] = k;
-        }
-        return R;
-    }
-    // by (diagonal, t); heads and tails of the runs; back by (t, q)
-    const int n2 = seed_pow2(R);
-    for (int i = tid; i < n2; i += SEED_THREADS) {
-        const uint64_t h = hits[i];
-        const uint32_t t = (uint32_t)(h >> 32), q = (uint32_t)h;
-        hits[i] = i < R ? (uint64_t)(t - q + 0x80000000u) << 32 | t : ~0ull;
-    }
-    __syncthreads();
-    seed_bitonic(hits, nullptr, n2);
-    int N = 0;
-    for (int base = 0; base < R; base += SEED_THREADS) {
-        const int i = base + tid;
-        bool head = false, tail = false;
-        uint64_t me = 0;
-        if (i < R) {
-            me = hits[i];
-            const uint64_t prev = i > 0 ? hits[i - 1] : 0, next = i + 1 < R ? hits[i + 1] : 0;
-            head = i == 0 || (prev >> 32) != (me >> 32) || me > prev + (uint64_t)k; // (the same diagonal: the difference is t's)
-            tail = i + 1 == R || (next >> 32) != (me >> 32) || next > me + (uint64_t)k;
-        }
-        int total;
-        const int r = N + strand_block_scan(head ? 1 : 0, total) + (head ? 1 : 0) - 1; // the run this hit belongs to
-        const uint32_t t = (uint32_t)me, d = (uint32_t)(me >> 32);
-        if (head) run[r] = (uint64_t)t << 32 | (uint32_t)(t - d + 0x80000000u);
-        if (tail) len[r] = t + (uint32_t)k; // the run's end; its length once the head is known to all
-        N += total;
-    }
-    __syncthreads();
-    const int m2 = seed_pow2(N);
-    for (int i = tid; i < m2; i += SEED_THREADS) {
-        if (i < N) len[i] -= (uint32_t)(run[i] >> 32);
-        else run[i] = ~0ull, len[i] = 0;
-    }
-    __syncthreads();
-    seed_bitonic(run, len, m2);
-    for (int i = tid; i < N; i += SEED_THREADS) {
-        const uint64_t h = run[i];
-        st[i] = (int32_t)(h >> 32);
-        sq[i] = (int32_t)(uint32_t)h;
-        sl[i] = (int32_t)len[i];
-    }
-    __syncthreads(); // (the next row's runs go to the same place)
-    return N;
-}
 
 __global__ __launch_bounds__(SEED_THREADS) void sw_seed_strands_kernel(const SeedStrandsArgs aa)
 {
@@ -276,8 +55,8 @@ __global__ __launch_bounds__(SEED_THREADS) void sw_seed_strands_kernel(const See
             if (a.status) a.status[row + r] = status;
         };
         if (tl < 1 || ql < 1) {
-            finish(0, 0, STRAND_ST_BAD_ARG);
-            finish(1, 0, STRAND_ST_BAD_ARG);
+            finish(0, 0, SEED_ST_BAD_ARG);
+            finish(1, 0, SEED_ST_BAD_ARG);
             continue;
         }
         const uint8_t *const T = a.targets + a.t_start[p], *const Q = a.queries + a.q_start[p];
@@ -288,7 +67,7 @@ __global__ __launch_bounds__(SEED_THREADS) void sw_seed_strands_kernel(const See
         int nq0 = 0, nq1 = 0, R0 = 0, R1 = 0;
 #pragma nounroll
         for (int r = 0; r < 2; ++r) {
-            const int nq = strand_build_table(Q, nkq, k, w, r == 1, s.tab[r], reinterpret_cast<uint64_t *>(slot + r * sg.slot_bytes));
+            const int nq = seed_build_table(Q, nkq, k, w, r == 1, s_tab[r], reinterpret_cast<uint64_t *>(slot + r * sg.slot_bytes), STRAND_LDS_TAB);
             if (r) nq1 = nq;
             else nq0 = nq;
         }
@@ -296,14 +75,15 @@ __global__ __launch_bounds__(SEED_THREADS) void sw_seed_strands_kernel(const See
         // ---- (b) the window's sketch, once, against both.  R < 0: the row is refused
         if (nq0 > 0 || nq1 > 0)
             for (uint32_t p0 = 0; (int64_t)p0 < nkt; p0 += SEED_BLOCK) {
-                const int64_t lo = strand_sketch_block(T, nkt, k, w, p0, false);
+                const int64_t lo = seed_sketch_block(T, nkt, k, w, p0, false);
 #pragma nounroll
                 for (int r = 0; r < 2; ++r) {
                     const int nq = r ? nq1 : nq0, R = r ? R1 : R0;
                     if (nq <= 0 || R < 0) continue;
                     unsigned char *const half = slot + r * sg.slot_bytes;
-                    const uint64_t *const tab = nq > STRAND_LDS_TAB ? reinterpret_cast<const uint64_t *>(half) : s.tab[r];
-                    const int Rn = strand_probe_block(tab, nq, s.hits[r], reinterpret_cast<uint64_t *>(half + SEED_SLOT_TAB), R, p0, lo, a.max_occ, a.max_cand);
+                    const uint64_t *const tab = nq > STRAND_LDS_TAB ? reinterpret_cast<const uint64_t *>(half) : s_tab[r];
+                    const int Rn = seed_probe_block(tab, nq, s_hits[r], reinterpret_cast<uint64_t *>(half + SEED_SLOT_TAB), STRAND_LDS_HITS, R, p0, lo, a.max_occ,
+                                                    a.max_cand);
                     if (r) R1 = Rn;
                     else R0 = Rn;
                 }
@@ -315,15 +95,16 @@ __global__ __launch_bounds__(SEED_THREADS) void sw_seed_strands_kernel(const See
         for (int r = 0; r < 2; ++r) {
             const int nq = r ? nq1 : nq0, R = r ? R1 : R0;
             if (nq < 0 || R < 0) {
-                finish(r, 0, STRAND_ST_UNSUPPORTED);
+                finish(r, 0, SEED_ST_UNSUPPORTED);
                 continue;
             }
             unsigned char *const half = slot + r * sg.slot_bytes;
             const bool in_lds = R <= STRAND_LDS_HITS;
-            uint64_t *const hits = in_lds ? s.hits[r] : reinterpret_cast<uint64_t *>(half + SEED_SLOT_TAB);
-            uint64_t *const run = in_lds ? &s.tab[0][0] : reinterpret_cast<uint64_t *>(half);
-            uint32_t *const len = in_lds ? reinterpret_cast<uint32_t *>(&s.tab[0][0] + STRAND_LDS_HITS) : reinterpret_cast<uint32_t *>(half + SEED_SLOT_LEN);
-            const int N = strand_stage_row(hits, R, run, len, stage + (row + r) * 3 * a.max_cand, a.max_cand, k, a.merge);
+            uint64_t *const hits = in_lds ? s_hits[r] : reinterpret_cast<uint64_t *>(half + SEED_SLOT_TAB);
+            uint64_t *const run = in_lds ? &s_tab[0][0] : reinterpret_cast<uint64_t *>(half);
+            uint32_t *const len = in_lds ? reinterpret_cast<uint32_t *>(&s_tab[0][0] + STRAND_LDS_HITS) : reinterpret_cast<uint32_t *>(half + SEED_SLOT_LEN);
+            const int N = seed_stage_row<true>(hits, R, run, len, stage + (row + r) * 3 * a.max_cand, a.max_cand, k, a.merge);
+            __syncthreads(); // (the next row's runs go to the same place)
             finish(r, N, 0);
         }
     }
@@ -343,7 +124,7 @@ __global__ __launch_bounds__(256) void sw_select_strand_kernel(const SelectStran
         a.count[p] = bad ? -1 : strand ? K1 : K0;
         a.strand[p] = strand;
         if (a.score) a.score[p] = strand ? s1 : s0;
-        if (a.status) a.status[p] = bad ? STRAND_ST_BAD_ARG : 0;
+        if (a.status) a.status[p] = bad ? SEED_ST_BAD_ARG : 0;
     }
 }
 
@@ -356,12 +137,7 @@ __global__ __launch_bounds__(1024) void sw_select_strand_scan_kernel(const Selec
         const int64_t p = base + tid;
         const int cnt = p < a.n ? a.count[p] : 0;
         const int64_t own = cnt > 0 ? cnt : 0;
-        int64_t incl = own;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
+        const int64_t incl = wave_inclusive_sum(own);
         if (lane == 63) wave_sum[wave] = incl;
         __syncthreads();
         int64_t before = carry, all = 0;
