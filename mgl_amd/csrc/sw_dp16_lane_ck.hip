@@ -763,11 +763,17 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
         }
     };
     // The carry row and the query are read ONE GROUP OF FOUR COLUMNS AHEAD: what a group needs was requested at the top of the
-    // group before it, so its latency -- and the acknowledgements of the stores issued in between, which s_waitcnt vmcnt counts
-    // in the same queue -- hides behind a thousand instructions of arithmetic instead of stalling the wave at every group (measured
-    // before: a third of the waves' lifetime in s_waitcnt at two waves per SIMD).  Reads past column ql stay inside the wave's own
-    // region (the next kept row follows; the narrow kernels' last carry row, "entering strip `strips`", is allocated and never
-    // written) and are never used.
+    // group before it, so its latency hides behind a thousand instructions of arithmetic.  s_waitcnt vmcnt counts loads and stores in
+    // one queue, in order, so a wait for those loads may leave in flight exactly the stores issued behind them -- the group's own
+    // kept-row stores -- and the compiler counts them where every path into the wait has issued the same operations.  The loop's
+    // header is not such a place: the prologue arrives with its loads newest in the queue, the latch with the group's stores
+    // behind them, and the merged wait was vmcnt(0) -- every group drained the stores it had just issued.  So the prefetched
+    // values are CONSUMED where the paths are still apart (the empty asm statements: once in front of the loop, the full wait, once
+    // per strip; and at the bottom of the body, behind the stores): each wait then stands in the body with its own count, none at
+    // the header, and a group's stores have until the next group's loads are consumed.  scripts/lane_ck_waits.py lists the waits
+    // of a build; a count is right when the newest operation it waits for is a load (docs/history.md C.000f).
+    // Reads past column ql stay inside the wave's own region (the next kept row follows; the narrow kernels' last carry row,
+    // "entering strip `strips`", is allocated and never written) and are never used.
     if (NARROW) {
         // the group's H as one 16-byte vector and its difference bytes as one 8-byte vector; E of a column is H minus its zero-extended
         // byte.  (A wave with a wide tail, ql = 1, 2, 5, fetches a narrow group where its tail stands -- inside the row, not used -- and
@@ -788,6 +794,7 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
         };
         fetch();
         unsigned nqa = qst[0], nqb = qst[64];
+        asm volatile("" : "+v"(nh.x), "+v"(nh.y), "+v"(nh.z), "+v"(nh.w), "+v"(nd.x), "+v"(nd.y), "+v"(nqa), "+v"(nqb)); // consumed: the prologue's wait stays in front of the loop
         for (; j + 3 <= ql; j += 4) {
             if (!(MGL_CK_ABLATE & 2) && j > 1 && ((j - 1) & (CK - 1)) == 0) save(); // (column 0 is a formula: no checkpoint)
             const uint4 th = nh;
@@ -803,6 +810,7 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
             one_column(top(th, td, 3), qa, qb, 3);
             mid_group(4);
             if (LAST == NOT_LAST) carry_group(4);
+            asm volatile("" : "+v"(nh.x), "+v"(nh.y), "+v"(nh.z), "+v"(nh.w), "+v"(nd.x), "+v"(nd.y), "+v"(nqa), "+v"(nqb)); // consumed behind the group's stores: no wait at the header
         }
         if (j <= ql) { // the last one to three columns (j - 1 is a multiple of four here)
             if (j > 1 && ((j - 1) & (CK - 1)) == 0) save();
@@ -832,6 +840,7 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
     } else {
         uint2 n0 = bp[0], n1 = bp[64], n2 = bp[128], n3 = bp[192];
         unsigned nqa = qst[0], nqb = qst[64];
+        asm volatile("" : "+v"(n0.x), "+v"(n0.y), "+v"(n1.x), "+v"(n1.y), "+v"(n2.x), "+v"(n2.y), "+v"(n3.x), "+v"(n3.y), "+v"(nqa), "+v"(nqb)); // consumed: the prologue's wait stays in front of the loop
         for (; j + 3 <= ql; j += 4) {
             if (!(MGL_CK_ABLATE & 2) && j > 1 && ((j - 1) & (CK - 1)) == 0) save(); // (column 0 is a formula: no checkpoint)
             const uint2 top0 = n0, top1 = n1, top2 = n2, top3 = n3;
@@ -848,6 +857,7 @@ __device__ __forceinline__ void ck_strip(const int k, const int tl, const int ql
             one_column(top1, qa, qb, 1);
             one_column(top2, qa, qb, 2);
             one_column(top3, qa, qb, 3);
+            asm volatile("" : "+v"(n0.x), "+v"(n0.y), "+v"(n1.x), "+v"(n1.y), "+v"(n2.x), "+v"(n2.y), "+v"(n3.x), "+v"(n3.y), "+v"(nqa), "+v"(nqb)); // consumed behind the group's stores: no wait at the header
         }
         if (j <= ql) { // the last one to three columns (j - 1 is a multiple of four here)
             if (j > 1 && ((j - 1) & (CK - 1)) == 0) save();
@@ -1042,11 +1052,14 @@ __device__ __forceinline__ void ck_block(const int sA, const int bA, const int s
                 da[x] = db[x] = make_uint2(0u, 0u);
             }
             const int glast = (g.ql - 1) >> 2;
+            // (the group's offset by a 24-BIT multiply -- a group index is below 2^14 here: as a 32-bit multiply-add the compiler took
+            // v_mad_u64_u32, whose 64-bit addend was a register pair with an unused half, and where that half was the register of a
+            // query dword still in flight the byte-compare form waited vmcnt(0) in front of pair B's loads: for pair A's as well)
             if (needA) {
                 const unsigned row = wm.kept_row_off(sA, g.ql);
 #pragma unroll
                 for (int x = 0; x < 2; ++x) {
-                    const unsigned grp = row + (unsigned)(min(bA * (CK / 4) + 2 * gg + x, glast) * 1536);
+                    const unsigned grp = row + __umul24((unsigned)min(bA * (CK / 4) + 2 * gg + x, glast), 1536u);
                     ha[x] = WaveMem::at32<uint4>(wm.rows, grp + 16u * wm.lane);
                     da[x] = WaveMem::at32<uint2>(wm.rows, grp + 1024u + 8u * wm.lane);
                 }
@@ -1055,7 +1068,7 @@ __device__ __forceinline__ void ck_block(const int sA, const int bA, const int s
                 const unsigned row = wm.kept_row_off(sB, g.ql);
 #pragma unroll
                 for (int x = 0; x < 2; ++x) {
-                    const unsigned grp = row + (unsigned)(min(bB * (CK / 4) + 2 * gg + x, glast) * 1536);
+                    const unsigned grp = row + __umul24((unsigned)min(bB * (CK / 4) + 2 * gg + x, glast), 1536u);
                     hb[x] = WaveMem::at32<uint4>(wm.rows, grp + 16u * wm.lane);
                     db[x] = WaveMem::at32<uint2>(wm.rows, grp + 1024u + 8u * wm.lane);
                 }
