@@ -746,6 +746,21 @@ int mgl_sw_chain_anchors_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
                                       int32_t *d_chain_score_out, int32_t *d_f_out, int32_t *d_pred_out, int32_t *d_status_out);
 
 /*
+ * ANCHOR CHAINING IN GROUPS (NOT a reference function; opt-in): mgl_sw_chain_anchors_batch_device with one more required array,
+ * d_cand_group (int32 per candidate; mgl_sw_index_contig_of_batch_device writes it).  Defined by tests/contig_textbook.py
+ * (chain_dp_grouped).  j may precede i only if, beside that entry's inequalities, group[j] == group[i] and group[i] >= 0 -- the rule
+ * minimap2 applies with rid.  A candidate of group -1 is a chain of its own with f = l.  Group values are not checked.  The outputs,
+ * the statuses and their order, the workspace, the scan and the pack are that entry's; a null d_cand_group is MGL_SW_ERR_BAD_ARG
+ * before any device work.  Device work: sw_chain_dp_kernel<true> in place of <false>.  DESIGN.md section 9m.
+ */
+int mgl_sw_chain_anchors_grouped_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const int32_t *d_t_len, const int32_t *d_q_len,
+                                              const int64_t *d_cand_start, const int32_t *d_cand_t, const int32_t *d_cand_q, const int32_t *d_cand_len,
+                                              const int32_t *d_cand_group, int64_t total_cand, int max_cand, int max_pred, int max_dist_t, int max_dist_q,
+                                              int bw, int pen_gap, int pen_skip, int64_t *d_chain_start_out, int32_t *d_chain_t_out, int32_t *d_chain_q_out,
+                                              int32_t *d_chain_len_out, int32_t *d_chain_score_out, int32_t *d_f_out, int32_t *d_pred_out,
+                                              int32_t *d_status_out);
+
+/*
  * SEEDING (NOT a reference function; opt-in): the seed stage in front of mgl_sw_chain_anchors_batch_device.  Reads and their windows go
  * in; every pair's candidate anchors come out, on the device, in the CSR layout and the order that entry reads.  A read is seeded
  * against its OWN window -- no index.  Integers only; defined by tests/seed_textbook.py.  Per pair p: the window T (tl = d_t_len[p]
@@ -858,8 +873,8 @@ int mgl_sw_select_strand_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
  * between them, rocPRIM's radix sort over bits [0, 32 + 2k), sw_index_split_kernel, sw_index_bucket_kernel (a table over the top
  * min(2k, 24, max(10, ceil(log2 M))) bits of a key).  Scratch of the build -- 16 bytes per entry and the sort's -- is freed before it
  * returns.  No MGL_SW_KERNEL_* id.
- * LIMITS: ONE reference sequence (contigs concatenated by the caller need at least k non-ACGT bytes between them, and a chain may
- * still span a boundary); ref_len < 2^31; k <= 16; the build synchronises.
+ * LIMITS: this build knows ONE reference sequence; a reference of several contigs goes through mgl_sw_index_build_contigs_device
+ * below, which keeps chains and windows inside a contig; ref_len < 2^31; k <= 16; the build synchronises.
  */
 typedef struct mgl_sw_index mgl_sw_index;
 typedef struct mgl_sw_index_info {
@@ -870,6 +885,37 @@ int mgl_sw_index_build_device(mgl_sw_ctx *ctx, void *stream, const uint8_t *d_re
 void mgl_sw_index_destroy(mgl_sw_index *idx);
 int mgl_sw_index_get_info(const mgl_sw_index *idx, mgl_sw_index_info *out);
 int mgl_sw_index_export_device(const mgl_sw_index *idx, void *stream, uint32_t *d_keys_out, int32_t *d_pos_out, int64_t capacity);
+
+/*
+ * A REFERENCE OF MANY CONTIGS (NOT a reference function; opt-in): DESIGN.md section 9m; defined by tests/contig_textbook.py.  The
+ * reference stays ONE device buffer of ref_len < 2^31 bytes.  Contig c occupies [contig_start[c], contig_start[c] + contig_len[c]);
+ * the contigs and the gaps between them tile the buffer: contig_start[0] = 0, contig_len[c] >= 1, contig_start[c] + contig_len[c] <
+ * contig_start[c + 1] (at least ONE gap byte between two contigs), the last contig ends at ref_len, and every gap byte is one the seed
+ * stage maps to no base (anything but upper-case A, C, G, T; N for instance).  One such byte is enough: no valid k-mer holds it, so no
+ * k-mer crosses a boundary, and two hits on either side of it are at least k + 1 apart in t, so the merge cannot join them.
+ * The index's entries stay tests/index_textbook.py's build_index(buffer, k, w): the sketch of the WHOLE buffer.  A window of w
+ * positions that straddles a gap selects among the valid positions it sees on both sides -- that is part of the definition, not the
+ * sketch of every contig on its own.
+ * mgl_sw_index_build_contigs_device: contig_start and contig_len are HOST arrays (int64, n_contigs in 1 .. 2^20).  The rules above but
+ * the gap bytes are checked on the host: MGL_SW_ERR_BAD_ARG before any device work, as for every argument of
+ * mgl_sw_index_build_device.  sw_contig_gap_kernel (a workgroup per gap) reads the gap bytes: one that is a base is
+ * MGL_SW_ERR_BAD_ARG too, behind a synchronisation of `stream`.  Then the build of mgl_sw_index_build_device runs as it is; the handle
+ * keeps a device copy of the table (start and end, int32: 8 bytes per contig, not counted in mgl_sw_index_info.bytes).  *out is null
+ * on every failure.
+ * mgl_sw_index_get_contigs: *n_out = the number of contigs; with capacity >= that, the table into the host arrays start_out and
+ * len_out (capacity 0 and both null: *n_out alone).  An index of mgl_sw_index_build_device reports ONE contig [0, ref_len), and the two
+ * entries below treat it so.  MGL_SW_ERR_BAD_ARG for a null index or n_out, one null array, or a capacity below the number.
+ * mgl_sw_index_contig_of_batch_device: per anchor i of `total` (0 .. 2^30; d_t, d_len, d_group_out int32 device arrays) group = c
+ * where contig c holds [t, t + l) whole, -1 otherwise: t < 0, l < 1, inside a gap, or over a contig's end.  sw_contig_of_kernel, a
+ * thread per anchor, the table searched in LDS up to 4096 contigs and in memory beyond; on `stream`, no workspace, no synchronisation.
+ * MGL_SW_ERR_BAD_ARG before any device work for a null pointer or total outside its range; MGL_SW_ERR_DEVICE without a GPU.
+ * No MGL_SW_KERNEL_* id.  LIMITS: contigs have no names here; ref_len < 2^31.
+ */
+int mgl_sw_index_build_contigs_device(mgl_sw_ctx *ctx, void *stream, const uint8_t *d_ref, int64_t ref_len, const int64_t *contig_start,
+                                      const int64_t *contig_len, int64_t n_contigs, int k, int w, mgl_sw_index **out);
+int mgl_sw_index_get_contigs(const mgl_sw_index *idx, int64_t capacity, int64_t *start_out, int64_t *len_out, int64_t *n_out);
+int mgl_sw_index_contig_of_batch_device(mgl_sw_ctx *ctx, void *stream, const mgl_sw_index *idx, int64_t total, const int32_t *d_t,
+                                        const int32_t *d_len, int32_t *d_group_out);
 
 /*
  * SEEDING AGAINST THE INDEX (NOT a reference function; opt-in): mgl_sw_seed_strands_batch_device with the whole reference for every
@@ -917,6 +963,21 @@ int mgl_sw_locate_window_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
                                       const int64_t *d_anchor_start, const int32_t *d_anchor_t, const int32_t *d_anchor_q,
                                       const int32_t *d_anchor_len, int64_t total_anchors, int slack, int max_tl, int64_t *d_t_start_out,
                                       int32_t *d_t_len_out, int32_t *d_anchor_t_out, int32_t *d_status_out);
+
+/*
+ * THE WINDOW OF A CHAIN INSIDE ITS CONTIG (NOT a reference function; opt-in): mgl_sw_locate_window_batch_device with the index in
+ * place of ref_len, and d_rid_out (int32, n).  Defined by tests/contig_textbook.py (locate_window_contigs).  With c the contig of the
+ * pair's first anchor: an anchor in another contig or in none (mgl_sw_index_contig_of_batch_device's -1) is MGL_SW_ERR_BAD_ARG for
+ * the pair; lo = max(start[c], t0 - q0 - slack), hi = min(end[c], tK + lK + (ql - qK - lK) + slack).  d_t_start_out stays in the
+ * BUFFER's coordinates -- the alignment reads the reference in place --; d_rid_out[p] = c for a kept pair, -1 for an unmapped or a
+ * refused one.  Every other check, output and the in-place rule are mgl_sw_locate_window_batch_device's, and so are the call-level
+ * refusals (a null index or d_rid_out among them).  Device work on `stream`, no synchronisation, no workspace:
+ * sw_locate_window_contigs_kernel (a wave per pair).  No MGL_SW_KERNEL_* id.
+ */
+int mgl_sw_locate_window_contigs_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const mgl_sw_index *idx, const int32_t *d_q_len,
+                                              const int64_t *d_anchor_start, const int32_t *d_anchor_t, const int32_t *d_anchor_q,
+                                              const int32_t *d_anchor_len, int64_t total_anchors, int slack, int max_tl, int64_t *d_t_start_out,
+                                              int32_t *d_t_len_out, int32_t *d_anchor_t_out, int32_t *d_rid_out, int32_t *d_status_out);
 
 /*
  * SECONDARY CHAINS AND MAPPING QUALITY (NOT a reference function; opt-in): behind mgl_sw_chain_anchors_batch_device, beside the strand

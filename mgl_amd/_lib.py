@@ -37,7 +37,9 @@ SYMBOLS = (
     "mgl_sw_chain_anchors_batch_device", "mgl_sw_seed_batch_device", "mgl_sw_seed_strands_batch_device",
     "mgl_sw_select_strand_batch_device", "mgl_sw_index_build_device", "mgl_sw_index_destroy", "mgl_sw_index_get_info",
     "mgl_sw_index_export_device", "mgl_sw_seed_index_batch_device", "mgl_sw_locate_window_batch_device",
-    "mgl_sw_rank_chains_batch_device", "mgl_sw_describe_alignments_batch_device",
+    "mgl_sw_rank_chains_batch_device", "mgl_sw_describe_alignments_batch_device", "mgl_sw_index_build_contigs_device",
+    "mgl_sw_index_get_contigs", "mgl_sw_index_contig_of_batch_device", "mgl_sw_chain_anchors_grouped_batch_device",
+    "mgl_sw_locate_window_contigs_batch_device",
 )
 # MGL_SW_VERSION of the include/mgl_sw.h this mirror was written against: the structs below (Plan, Timing) are that header's, and the
 # library writes sizeof(ITS struct) through the pointers it is given -- so a library of another version is refused at load time
@@ -212,6 +214,11 @@ def lib():
     L.mgl_sw_index_export_device.argtypes = [vp, vp, vp, vp, C.c_int64]
     L.mgl_sw_seed_index_batch_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp] + [C.c_int] * 5 + [C.c_int64] + [vp] * 7
     L.mgl_sw_locate_window_batch_device.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int] + [vp] * 4
+    L.mgl_sw_index_build_contigs_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int, C.POINTER(vp)]
+    L.mgl_sw_index_get_contigs.argtypes = [vp, C.c_int64, vp, vp, i64p]
+    L.mgl_sw_index_contig_of_batch_device.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp]
+    L.mgl_sw_chain_anchors_grouped_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int64] + [C.c_int] * 7 + [vp] * 8
+    L.mgl_sw_locate_window_contigs_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int] + [vp] * 5
     L.mgl_sw_rank_chains_batch_device.argtypes = [vp, vp, C.c_int64, C.c_int, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp] + [C.c_int] * 5 + [vp] * 7
     L.mgl_sw_describe_alignments_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp,
                                                           C.c_int]

@@ -68,9 +68,10 @@ struct ChainDpArgs {
     int32_t *chain_score;                        // n
     int32_t *f_out, *pred_out;                   // optional, per candidate
     int32_t *status;                             // optional, per read
+    const int32_t *cand_group;                   // per candidate; null: sw_chain_dp_kernel<false>, every candidate in one group
 };
 
-hipError_t launch_chain_dp(const ChainDpArgs &a, hipStream_t stream);      // sw_chain_dp_kernel: count, stage, score, f, pred, status
+hipError_t launch_chain_dp(const ChainDpArgs &a, hipStream_t stream);      // sw_chain_dp_kernel<cand_group != null>: count, stage, score, f, pred, status
 hipError_t launch_chain_dp_scan(const ChainDpArgs &a, hipStream_t stream); // chain_start = the prefix sum of count
 hipError_t launch_chain_dp_pack(const ChainDpArgs &a, hipStream_t stream); // the chains into their CSR place
 

@@ -1,5 +1,5 @@
-// sw_chain_dp.hip -- the three kernels of mgl_sw_chain_anchors_batch_device (the function is
-// tests/chain_dp_textbook.py's).  sw_chain_dp.h describes the workspace they share with the host side.
+// sw_chain_dp.hip -- the three kernels of mgl_sw_chain_anchors_batch_device and of its grouped form (DESIGN.md sections 9g and 9m; the
+// functions are tests/chain_dp_textbook.py's and tests/contig_textbook.py's chain_dp_grouped).  sw_chain_dp.h describes the workspace they share with the host side.
 //
 // sw_chain_dp_kernel, the hot path: one wave per read, persistent over the reads.  The FORWARD form of the DP: the 64 lanes are a
 // ring, lane i mod 64 owns candidate i while its predecessors j = i - 64 .. i - 1 go by.  Step j: f(j) is final in lane j mod 64 --
@@ -24,6 +24,9 @@ namespace mgl_sw_dev {
 
 namespace {
 
+// GROUPED (mgl_sw_chain_anchors_grouped_batch_device): j may precede i only where both have the same group >= 0.  A lane carries its
+// candidate's group beside t, q and l, and the groups of the next two blocks beside nt and mt; a step reads j's from its lane.
+template <bool GROUPED>
 __global__ __launch_bounds__(64) void sw_chain_dp_kernel(const ChainDpArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_pred[];
@@ -66,6 +69,7 @@ __global__ __launch_bounds__(64) void sw_chain_dp_kernel(const ChainDpArgs a)
             continue;
         }
         const int32_t *const ct = a.cand_t + c0, *const cq = a.cand_q + c0, *const cl = a.cand_len + c0;
+        [[maybe_unused]] const int32_t *const cg = GROUPED ? a.cand_group + c0 : nullptr;
         __threadfence_block(); // (the trace-back of the wave's last read is done with the pred bytes)
         __builtin_amdgcn_wave_barrier();
 
@@ -74,11 +78,19 @@ __global__ __launch_bounds__(64) void sw_chain_dp_kernel(const ChainDpArgs a)
         int t = 0, q = 0, l = 0, nt = 0, nq = 0, nl = 0;
         if (idx < N) t = ct[idx], q = cq[idx], l = cl[idx];
         if (idx + 64 < N) nt = ct[idx + 64], nq = cq[idx + 64], nl = cl[idx + 64];
+        [[maybe_unused]] int g = -1, ng = -1;
+        if constexpr (GROUPED) {
+            if (idx < N) g = cg[idx];
+            if (idx + 64 < N) ng = cg[idx + 64];
+        }
         int f = l, pred = -1;
         int best_f = 0, best_i = 0;
         for (int base = 0; base < N; base += 64) {
             int mt = 0, mq = 0, ml = 0;
             if (base + 128 + lane < N) mt = ct[base + 128 + lane], mq = cq[base + 128 + lane], ml = cl[base + 128 + lane];
+            [[maybe_unused]] int mg = -1;
+            if constexpr (GROUPED)
+                if (base + 128 + lane < N) mg = cg[base + 128 + lane];
             int fin_f = 0, fin_p = -1;
             const int steps = min(64, N - base);
             for (int s = 0; s < steps; ++s) {
@@ -86,6 +98,8 @@ __global__ __launch_bounds__(64) void sw_chain_dp_kernel(const ChainDpArgs a)
                 const int fj = __builtin_amdgcn_readlane(f, s);
                 const int lj = __builtin_amdgcn_readlane(l, s);
                 const int te = __builtin_amdgcn_readlane(t, s) + lj, qe = __builtin_amdgcn_readlane(q, s) + lj;
+                [[maybe_unused]] int gj = 0;
+                if constexpr (GROUPED) gj = __builtin_amdgcn_readlane(g, s);
                 if (lane == s) { // f(j) is final: kept aside, and the lane takes candidate j + 64
                     fin_f = f;
                     fin_p = pred;
@@ -95,6 +109,7 @@ __global__ __launch_bounds__(64) void sw_chain_dp_kernel(const ChainDpArgs a)
                     t = nt;
                     q = nq;
                     l = nl;
+                    if constexpr (GROUPED) g = ng;
                     f = nl;
                     pred = -1;
                     idx += 64;
@@ -103,7 +118,8 @@ __global__ __launch_bounds__(64) void sw_chain_dp_kernel(const ChainDpArgs a)
                 const int dt = (int)((uint32_t)t - (uint32_t)te), dq = (int)((uint32_t)q - (uint32_t)qe);
                 const int diff = (int)((uint32_t)dt - (uint32_t)dq);
                 const uint32_t dd = (uint32_t)(diff < 0 ? -diff : diff);
-                const bool ok = idx < N && idx - j <= max_pred && dt >= 0 && dq >= 0 && dt <= mdt && dq <= mdq && dd <= (uint32_t)bw;
+                bool ok = idx < N && idx - j <= max_pred && dt >= 0 && dq >= 0 && dt <= mdt && dq <= mdq && dd <= (uint32_t)bw;
+                if constexpr (GROUPED) ok = ok && g == gj && g >= 0;
                 const uint32_t dg = (uint32_t)(dt < dq ? dt : dq);
                 const int pen = (int)((pen_gap * dd + pen_skip * dg) >> 8) + ((31 - __clz((int)(dd + 1u))) >> 1);
                 const int cand = (int)((uint32_t)fj + (uint32_t)l - (uint32_t)pen);
@@ -122,6 +138,7 @@ __global__ __launch_bounds__(64) void sw_chain_dp_kernel(const ChainDpArgs a)
             nt = mt;
             nq = mq;
             nl = ml;
+            if constexpr (GROUPED) ng = mg;
         }
 
         // ---- the chain's end: the largest f, then the smallest index
@@ -211,7 +228,8 @@ hipError_t launch_chain_dp(const ChainDpArgs &a, hipStream_t stream)
     if (!a.count || !a.stage || !a.chain_score || !a.cand_start) return hipErrorInvalidValue;
     // where pred lives: LDS that holds max_cand bytes, or a slot that does
     if (a.slot_bytes == 0 ? (a.lds_bytes < a.max_cand || a.lds_bytes > CHAIN_DP_LDS_PRED) : (!a.ws || a.slot_bytes < a.max_cand)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sw_chain_dp_kernel, dim3((unsigned)a.waves), dim3(64), (size_t)a.lds_bytes, stream, a);
+    if (a.cand_group) hipLaunchKernelGGL(sw_chain_dp_kernel<true>, dim3((unsigned)a.waves), dim3(64), (size_t)a.lds_bytes, stream, a);
+    else hipLaunchKernelGGL(sw_chain_dp_kernel<false>, dim3((unsigned)a.waves), dim3(64), (size_t)a.lds_bytes, stream, a);
     return hipGetLastError();
 }
 

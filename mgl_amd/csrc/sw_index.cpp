@@ -1,4 +1,6 @@
-// sw_index.cpp -- the minimizer index of one reference (mgl_sw_index_build_device, _destroy, _get_info, _export_device), the seed stage
+// sw_index.cpp -- the minimizer index of one reference (mgl_sw_index_build_device, _build_contigs_device, _destroy, _get_info,
+// _get_contigs, _export_device), the contig of an anchor (mgl_sw_index_contig_of_batch_device, and the window inside a contig,
+// mgl_sw_locate_window_contigs_batch_device: DESIGN.md section 9m), the seed stage
 // that probes it (mgl_sw_seed_index_batch_device) and the stage that turns a read's chain into a window of the reference
 // (mgl_sw_locate_window_batch_device): include/mgl_sw.h, DESIGN.md section 9j.  Host side only: argument checks, the index's own
 // allocations, one workspace for the seed stage, launches on the caller's stream.  The build synchronises the stream -- it has to
@@ -11,6 +13,7 @@
 #include <cstdint>
 #include <mutex>
 #include <new>
+#include <vector>
 
 #include "sw_index.h"
 #include "sw_stage_host.h"
@@ -25,6 +28,11 @@ struct mgl_sw_index {
     uint32_t *keys = nullptr;   // entries (at least one allocated)
     int32_t *pos = nullptr;
     uint32_t *bucket = nullptr; // 2^bucket_bits + 1
+    // ---- the contig table (mgl_sw_index_build_contigs_device); n_contigs = 0: none, one contig [0, ref_len)
+    int64_t n_contigs = 0;
+    int32_t *contigs = nullptr;         // device: n_contigs starts, then n_contigs ends
+    std::vector<int64_t> contig_start;  // host, as the caller gave them
+    std::vector<int64_t> contig_len;
 };
 
 namespace {
@@ -57,6 +65,16 @@ IndexView view_of(const mgl_sw_index *idx)
     v.k = idx->k;
     v.w = idx->w;
     v.bucket_bits = idx->bucket_bits;
+    return v;
+}
+
+ContigView contigs_of(const mgl_sw_index *idx)
+{
+    ContigView v{};
+    v.start = idx->contigs;
+    v.end = idx->contigs ? idx->contigs + idx->n_contigs : nullptr;
+    v.n = (int32_t)idx->n_contigs;
+    v.ref_len = (int32_t)idx->ref_len;
     return v;
 }
 
@@ -137,10 +155,100 @@ void mgl_sw_index_destroy(mgl_sw_index *idx)
     if (!idx) return;
     int was = -1;
     const bool moved = hipGetDevice(&was) == hipSuccess && was != idx->device && hipSetDevice(idx->device) == hipSuccess;
-    for (void *p : {static_cast<void *>(idx->keys), static_cast<void *>(idx->pos), static_cast<void *>(idx->bucket)})
+    for (void *p : {static_cast<void *>(idx->keys), static_cast<void *>(idx->pos), static_cast<void *>(idx->bucket), static_cast<void *>(idx->contigs)})
         if (p) (void)hipFree(p);
     if (moved) (void)hipSetDevice(was);
     delete idx;
+}
+
+int mgl_sw_index_build_contigs_device(mgl_sw_ctx *ctx, void *stream, const uint8_t *d_ref, int64_t ref_len, const int64_t *contig_start,
+                                      const int64_t *contig_len, int64_t n_contigs, int k, int w, mgl_sw_index **out)
+{
+    static const char *const entry = "mgl_sw_index_build_contigs_device";
+    if (out) *out = nullptr;
+    const char *bad = nullptr;
+    if (!out) bad = "null out";
+    else if (!d_ref) bad = "null reference";
+    else if (ref_len < 1 || ref_len > INDEX_MAX_REF) bad = "ref_len outside 1 .. 2^31 - 1";
+    else if (k < SEED_MIN_K || k > SEED_MAX_K) bad = "k outside 4 .. 16";
+    else if (w < 1 || w > SEED_MAX_W) bad = "w outside 1 .. 32";
+    else if (!contig_start || !contig_len) bad = "null contig array";
+    else if (n_contigs < 1 || n_contigs > CONTIG_MAX) bad = "n_contigs outside 1 .. 2^20";
+    else if (contig_start[0] != 0) bad = "the first contig does not start at 0";
+    else {
+        for (int64_t c = 0; c < n_contigs && !bad; ++c) {
+            const int64_t s = contig_start[c], l = contig_len[c];
+            if (s < 0 || s >= ref_len) bad = "a contig starts outside the reference";
+            else if (l < 1 || l > ref_len - s) bad = "a contig's length is below 1 or leaves the reference";
+            else if (c + 1 < n_contigs && s + l >= contig_start[c + 1]) bad = "no gap byte between two contigs";
+            else if (c + 1 == n_contigs && s + l != ref_len) bad = "the last contig does not end at ref_len";
+        }
+    }
+    if (bad) return refuse(ctx, entry, bad);
+    if (!ctx) return no_context();
+
+    // ---- the table on the device and the gap bytes looked at, under the context's lock; the build below takes it again
+    std::vector<int32_t> table((size_t)(2 * n_contigs));
+    for (int64_t c = 0; c < n_contigs; ++c) {
+        table[(size_t)c] = (int32_t)contig_start[c];
+        table[(size_t)(n_contigs + c)] = (int32_t)(contig_start[c] + contig_len[c]);
+    }
+    int32_t *d_table = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx_mutex(ctx));
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        hipError_t he = hipSetDevice(ctx_device(ctx));
+        if (he != hipSuccess) return ctx_hip_fail(ctx, he, "hipSetDevice");
+        Scratch flag;
+        if ((he = flag.get(4)) != hipSuccess) return ctx_hip_fail(ctx, he, "hipMalloc (gap flag)");
+        if ((he = hipMalloc(reinterpret_cast<void **>(&d_table), table.size() * 4)) != hipSuccess) return ctx_hip_fail(ctx, he, "hipMalloc (contig table)");
+        auto give_up = [&](hipError_t e, const char *where) {
+            (void)hipFree(d_table);
+            return ctx_hip_fail(ctx, e, where);
+        };
+        ContigView cv{d_table, d_table + n_contigs, (int32_t)n_contigs, (int32_t)ref_len};
+        int32_t base_in_gap = 0;
+        if ((he = hipMemcpyAsync(d_table, table.data(), table.size() * 4, hipMemcpyHostToDevice, st)) != hipSuccess) return give_up(he, "hipMemcpyAsync (contig table)");
+        if ((he = hipMemsetAsync(flag.p, 0, 4, st)) != hipSuccess) return give_up(he, "hipMemsetAsync (gap flag)");
+        if ((he = launch_contig_gaps(d_ref, cv, static_cast<int32_t *>(flag.p), st)) != hipSuccess) return give_up(he, "launch_contig_gaps");
+        if ((he = hipMemcpyAsync(&base_in_gap, flag.p, 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return give_up(he, "hipMemcpyAsync (gap flag)");
+        if ((he = hipStreamSynchronize(st)) != hipSuccess) return give_up(he, "hipStreamSynchronize (gaps)");
+        if (base_in_gap) {
+            (void)hipFree(d_table);
+            return ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, "mgl_sw_index_build_contigs_device: a gap between two contigs holds a base");
+        }
+    }
+
+    // ---- the existing build as it is; the handle takes the table
+    mgl_sw_index *idx = nullptr;
+    const int rc = mgl_sw_index_build_device(ctx, stream, d_ref, ref_len, k, w, &idx);
+    if (rc != MGL_SW_OK) {
+        (void)hipFree(d_table);
+        return rc;
+    }
+    idx->n_contigs = n_contigs;
+    idx->contigs = d_table;
+    idx->contig_start.assign(contig_start, contig_start + n_contigs);
+    idx->contig_len.assign(contig_len, contig_len + n_contigs);
+    *out = idx;
+    return MGL_SW_OK;
+}
+
+int mgl_sw_index_get_contigs(const mgl_sw_index *idx, int64_t capacity, int64_t *start_out, int64_t *len_out, int64_t *n_out)
+{
+    if (!idx || !n_out) return MGL_SW_ERR_BAD_ARG;
+    const int64_t n = idx->n_contigs > 0 ? idx->n_contigs : 1;
+    *n_out = n;
+    if (!start_out && !len_out && capacity == 0) return MGL_SW_OK; // a sizing call
+    if (!start_out || !len_out || capacity < n) return MGL_SW_ERR_BAD_ARG;
+    if (idx->n_contigs == 0) {
+        start_out[0] = 0;
+        len_out[0] = idx->ref_len;
+    } else {
+        std::copy(idx->contig_start.begin(), idx->contig_start.end(), start_out);
+        std::copy(idx->contig_len.begin(), idx->contig_len.end(), len_out);
+    }
+    return MGL_SW_OK;
 }
 
 int mgl_sw_index_get_info(const mgl_sw_index *idx, mgl_sw_index_info *out)
@@ -277,6 +385,76 @@ int mgl_sw_locate_window_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, 
     a.status = d_status_out;
     he = launch_locate_window(a, stage.st);
     if (he != hipSuccess) return stage.fail(he, "launch_locate_window");
+    return stage.done(); // (no workspace: the timing record is not touched)
+}
+
+int mgl_sw_index_contig_of_batch_device(mgl_sw_ctx *ctx, void *stream, const mgl_sw_index *idx, int64_t total, const int32_t *d_t, const int32_t *d_len,
+                                        int32_t *d_group_out)
+{
+    static const char *const entry = "mgl_sw_index_contig_of_batch_device";
+    const char *bad = nullptr;
+    if (!idx) bad = "null index";
+    else if (total < 0 || total > SEED_MAX_PAIRS) bad = "total outside 0 .. 2^30";
+    else if (!d_t || !d_len || !d_group_out) bad = "null array";
+    if (bad) return refuse(ctx, entry, bad);
+    if (!ctx) return no_context();
+    Stage stage(ctx, stream);
+    if (idx->device != ctx_device(ctx)) return ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, "mgl_sw_index_contig_of_batch_device: the index lives on another device");
+    hipError_t he = hipSetDevice(ctx_device(ctx));
+    if (he != hipSuccess) return stage.fail(he, "hipSetDevice");
+    ContigOfArgs a{};
+    a.cv = contigs_of(idx);
+    a.total = total;
+    a.t = d_t;
+    a.len = d_len;
+    a.group = d_group_out;
+    he = launch_contig_of(a, stage.st);
+    if (he != hipSuccess) return stage.fail(he, "launch_contig_of");
+    return stage.done(); // (no workspace: the timing record is not touched)
+}
+
+int mgl_sw_locate_window_contigs_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const mgl_sw_index *idx, const int32_t *d_q_len,
+                                              const int64_t *d_anchor_start, const int32_t *d_anchor_t, const int32_t *d_anchor_q,
+                                              const int32_t *d_anchor_len, int64_t total_anchors, int slack, int max_tl, int64_t *d_t_start_out,
+                                              int32_t *d_t_len_out, int32_t *d_anchor_t_out, int32_t *d_rid_out, int32_t *d_status_out)
+{
+    static const char *const entry = "mgl_sw_locate_window_contigs_batch_device";
+    const char *bad = nullptr;
+    if (n < 0 || n > SEED_MAX_PAIRS) bad = "n outside 0 .. 2^30";
+    else if (!idx) bad = "null index";
+    else if (!d_q_len || !d_anchor_start) bad = "null read array";
+    else if (!d_anchor_t || !d_anchor_q || !d_anchor_len) bad = "null anchor array";
+    else if (total_anchors < 0 || total_anchors > SEED_MAX_PAIRS) bad = "total_anchors outside 0 .. 2^30";
+    else if (slack < 0) bad = "slack below 0";
+    else if (max_tl < 1) bad = "max_tl below 1";
+    else if (!d_t_start_out || !d_t_len_out || !d_anchor_t_out || !d_rid_out) bad = "null output array";
+    if (bad) return refuse(ctx, entry, bad);
+    if (!ctx) return no_context();
+    Stage stage(ctx, stream);
+    if (idx->device != ctx_device(ctx)) return ctx_fail(ctx, MGL_SW_ERR_BAD_ARG, "mgl_sw_locate_window_contigs_batch_device: the index lives on another device");
+    hipError_t he = hipSetDevice(ctx_device(ctx));
+    if (he != hipSuccess) return stage.fail(he, "hipSetDevice");
+
+    LocateContigsArgs aa{};
+    LocateArgs &a = aa.l;
+    a.q_len = d_q_len;
+    a.anchor_start = d_anchor_start;
+    a.anchor_t = d_anchor_t;
+    a.anchor_q = d_anchor_q;
+    a.anchor_len = d_anchor_len;
+    a.n = n;
+    a.ref_len = idx->ref_len;
+    a.total_anchors = total_anchors;
+    a.slack = slack;
+    a.max_tl = max_tl;
+    a.t_start = d_t_start_out;
+    a.t_len = d_t_len_out;
+    a.anchor_t_out = d_anchor_t_out;
+    a.status = d_status_out;
+    aa.cv = contigs_of(idx);
+    aa.rid = d_rid_out;
+    he = launch_locate_window_contigs(aa, stage.st);
+    if (he != hipSuccess) return stage.fail(he, "launch_locate_window_contigs");
     return stage.done(); // (no workspace: the timing record is not touched)
 }
 

@@ -59,6 +59,32 @@ struct LocateArgs {
     int32_t *status;  // optional
 };
 
+// The contigs of a reference (mgl_sw_index_build_contigs_device; tests/contig_textbook.py): contig c is
+// [start[c], end[c]) of the buffer, ascending, with at least one byte that is no base between two of them.  n = 0: no table, ONE contig
+// [0, ref_len) -- what an index of mgl_sw_index_build_device is to the stages below.
+constexpr int64_t CONTIG_MAX = (int64_t)1 << 20;
+constexpr int CONTIG_LDS_MAX = 4096; // contigs whose start and end sw_contig_of_kernel searches in LDS (32 KiB)
+struct ContigView {
+    const int32_t *start, *end; // n each, device memory
+    int32_t n, ref_len;
+};
+
+struct ContigOfArgs {
+    ContigView cv;
+    int64_t total;
+    const int32_t *t, *len; // total each
+    int32_t *group;         // total
+};
+
+struct LocateContigsArgs {
+    LocateArgs l;     // ref_len unused: cv has it
+    ContigView cv;
+    int32_t *rid;     // n
+};
+
+hipError_t launch_contig_gaps(const uint8_t *ref, const ContigView &cv, int32_t *flag, hipStream_t stream); // sw_contig_gap_kernel: *flag = 1 for a base in a gap
+hipError_t launch_contig_of(const ContigOfArgs &a, hipStream_t stream);                    // sw_contig_of_kernel
+hipError_t launch_locate_window_contigs(const LocateContigsArgs &a, hipStream_t stream);   // sw_locate_window_contigs_kernel
 hipError_t launch_index_count(const IndexBuildArgs &a, hipStream_t stream);  // sw_index_sketch_kernel, pass 1: block_count
 hipError_t launch_index_scan(const IndexBuildArgs &a, hipStream_t stream);   // block_start
 hipError_t launch_index_write(const IndexBuildArgs &a, hipStream_t stream);  // sw_index_sketch_kernel, pass 2: entries

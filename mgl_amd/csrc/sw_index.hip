@@ -20,6 +20,11 @@
 // The table and the hits live in LDS up to SEED_LDS_TAB and SEED_LDS_HITS entries and in the workgroup's slot beyond.
 //
 // sw_locate_window_kernel: a wave per pair: the checks over the pair's anchors, the window, the anchors' t rebased in 4-byte stores.
+//
+// The contigs of a reference (the functions are tests/contig_textbook.py's; sw_index.h has the table):
+// sw_contig_gap_kernel (the build: a workgroup per gap looks for a base), sw_contig_of_kernel (a thread per anchor: the contig that holds
+// it, the table searched in LDS where it fits) and sw_locate_window_contigs_kernel (sw_locate_window_kernel inside the contig of the
+// pair's first anchor).
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -289,6 +294,90 @@ __global__ __launch_bounds__(64) void sw_locate_window_kernel(const LocateArgs a
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the contigs
+
+// the contig that holds [t, t + l): the last c with start[c] <= t, where t + l <= end[c] -- -1 where there is none: t < 0, l < 1, inside
+// a gap, or over a contig's end.  n = 0: one contig [0, ref_len), no table read.  `start` and `end`: pointers, or the LDS arrays themselves
+template <typename A>
+__device__ __forceinline__ int contig_find(const A &start, const A &end, const int n, const int ref_len, const int64_t t, const int64_t l)
+{
+    if (t < 0 || l < 1) return -1;
+    if (n == 0) return t + l <= ref_len ? 0 : -1;
+    int b = 0, e = n; // the first contig that starts beyond t
+    while (b < e) {
+        const int m = (b + e) >> 1;
+        if (start[m] <= t) b = m + 1;
+        else e = m;
+    }
+    return b > 0 && t + l <= end[b - 1] ? b - 1 : -1;
+}
+
+// a workgroup per gap: gap g lies between contig g and contig g + 1
+__global__ __launch_bounds__(256) void sw_contig_gap_kernel(const uint8_t *ref, const ContigView cv, int32_t *flag)
+{
+    const int g = blockIdx.x;
+    bool base = false;
+    for (int64_t i = (int64_t)cv.end[g] + threadIdx.x; i < cv.start[g + 1]; i += 256) base |= seed_code(ref[i]) < 4;
+    if (base) *flag = 1;
+}
+
+// a thread per anchor; the table staged in LDS where it fits
+template <bool LDS>
+__global__ __launch_bounds__(256) void sw_contig_of_kernel(const ContigOfArgs a)
+{
+    __shared__ int32_t s_start[LDS ? CONTIG_LDS_MAX : 1], s_end[LDS ? CONTIG_LDS_MAX : 1];
+    if constexpr (LDS) {
+        for (int i = threadIdx.x; i < a.cv.n; i += 256) s_start[i] = a.cv.start[i], s_end[i] = a.cv.end[i];
+        __syncthreads();
+    }
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.total; i += (int64_t)gridDim.x * 256) {
+        const int64_t t = a.t[i], l = a.len[i];
+        if constexpr (LDS) a.group[i] = contig_find(s_start, s_end, a.cv.n, a.cv.ref_len, t, l);
+        else a.group[i] = contig_find(a.cv.start, a.cv.end, a.cv.n, a.cv.ref_len, t, l);
+    }
+}
+
+// sw_locate_window_kernel with the window kept inside the contig of the read's first anchor; every anchor has to lie in that contig
+__global__ __launch_bounds__(64) void sw_locate_window_contigs_kernel(const LocateContigsArgs aa)
+{
+    const LocateArgs &a = aa.l;
+    const ContigView &cv = aa.cv;
+    const int lane = threadIdx.x;
+    for (int64_t p = blockIdx.x; p < a.n; p += gridDim.x) {
+        const int64_t ql = a.q_len[p], a0 = a.anchor_start[p], a1 = a.anchor_start[p + 1];
+        bool bad = ql < 1 || a0 < 0 || a1 < a0 || a1 > a.total_anchors;
+        const int64_t K = bad ? 0 : a1 - a0;
+        const int c = K > 0 ? contig_find(cv.start, cv.end, cv.n, cv.ref_len, a.anchor_t[a0], a.anchor_len[a0]) : -1; // (the same in every lane)
+        bool mine = false;
+        for (int64_t m = lane; m < K; m += 64) {
+            const int64_t t = a.anchor_t[a0 + m], q = a.anchor_q[a0 + m], l = a.anchor_len[a0 + m];
+            mine = mine || q < 0 || q + l > ql || contig_find(cv.start, cv.end, cv.n, cv.ref_len, t, l) != c;
+        }
+        bad = bad || (K > 0 && c < 0) || __any(mine);
+        int status = bad ? SEED_ST_BAD_ARG : 0;
+        int64_t lo = 0, hi = 0;
+        if (!bad && K > 0) { // (the first and the last anchor are read before any is rebased: the output may be the input)
+            const int64_t t0 = a.anchor_t[a0], q0 = a.anchor_q[a0];
+            const int64_t tK = a.anchor_t[a1 - 1], qK = a.anchor_q[a1 - 1], lK = a.anchor_len[a1 - 1];
+            const int64_t cs = cv.n ? cv.start[c] : 0, ce = cv.n ? cv.end[c] : cv.ref_len;
+            lo = t0 - q0 - a.slack;
+            lo = lo > cs ? lo : cs;
+            hi = tK + lK + (ql - qK - lK) + a.slack;
+            hi = hi < ce ? hi : ce;
+            if (hi - lo > a.max_tl) status = SEED_ST_UNSUPPORTED;
+        }
+        const bool kept = status == 0 && K > 0;
+        if (kept)
+            for (int64_t m = lane; m < K; m += 64) a.anchor_t_out[a0 + m] = (int32_t)(a.anchor_t[a0 + m] - lo);
+        if (lane == 0) {
+            a.t_start[p] = kept ? lo : 0;
+            a.t_len[p] = kept ? (int32_t)(hi - lo) : 0;
+            aa.rid[p] = kept ? c : -1;
+            if (a.status) a.status[p] = status;
+        }
+    }
+}
+
 int index_grid(const int64_t items, const int per_block)
 {
     const int64_t blocks = (items + per_block - 1) / per_block;
@@ -367,6 +456,41 @@ hipError_t launch_locate_window(const LocateArgs &a, hipStream_t stream)
     if (a.n < 1) return hipSuccess;
     if (!a.q_len || !a.anchor_start || !a.anchor_t || !a.anchor_q || !a.anchor_len || !a.t_start || !a.t_len || !a.anchor_t_out) return hipErrorInvalidValue;
     hipLaunchKernelGGL(sw_locate_window_kernel, dim3((unsigned)index_grid(a.n, 1)), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+static bool contig_view_ok(const ContigView &cv)
+{
+    return cv.ref_len >= 1 && cv.n >= 0 && cv.n <= CONTIG_MAX && (cv.n == 0 || (cv.start && cv.end));
+}
+
+hipError_t launch_contig_gaps(const uint8_t *ref, const ContigView &cv, int32_t *flag, hipStream_t stream)
+{
+    if (cv.n < 2) return hipSuccess;
+    if (!ref || !flag || !contig_view_ok(cv)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sw_contig_gap_kernel, dim3((unsigned)(cv.n - 1)), dim3(256), 0, stream, ref, cv, flag);
+    return hipGetLastError();
+}
+
+hipError_t launch_contig_of(const ContigOfArgs &a, hipStream_t stream)
+{
+    if (a.total < 1) return hipSuccess;
+    if (a.total > SEED_MAX_PAIRS || !a.t || !a.len || !a.group || !contig_view_ok(a.cv)) return hipErrorInvalidValue;
+    // a workgroup stages the table once and then strides over the anchors: no more workgroups than keep the device busy
+    const int64_t blocks = (a.total + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096));
+    if (a.cv.n <= CONTIG_LDS_MAX) hipLaunchKernelGGL(sw_contig_of_kernel<true>, grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(sw_contig_of_kernel<false>, grid, dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_locate_window_contigs(const LocateContigsArgs &aa, hipStream_t stream)
+{
+    const LocateArgs &a = aa.l;
+    if (a.n < 1) return hipSuccess;
+    if (!a.q_len || !a.anchor_start || !a.anchor_t || !a.anchor_q || !a.anchor_len || !a.t_start || !a.t_len || !a.anchor_t_out || !aa.rid) return hipErrorInvalidValue;
+    if (!contig_view_ok(aa.cv)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sw_locate_window_contigs_kernel, dim3((unsigned)index_grid(a.n, 1)), dim3(64), 0, stream, aa);
     return hipGetLastError();
 }
 

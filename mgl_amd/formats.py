@@ -249,9 +249,32 @@ def bam_pairs(path, window=None, seed=7, min_mapq=0):
 
 
 # --------------------------------------------------------------------------------------------- SAM / PAF
+def _targets(ref_name, ref_len):
+    """-> ([names], [lengths], many): ``ref_name`` and ``ref_len`` as one reference sequence (a string and a number) or as lists of
+    equal length, one entry per contig."""
+    if isinstance(ref_name, (str, bytes)):
+        return [ref_name.decode() if isinstance(ref_name, bytes) else ref_name], [int(ref_len)], False
+    names, lens = list(ref_name), [int(x) for x in ref_len]
+    if len(names) != len(lens) or not names:
+        raise ValueError("ref_name and ref_len: lists of one length, one entry per contig")
+    return names, lens, True
+
+
+def _target_of(result, k, names, lens, many):
+    """the (name, length) of the contig read ``k`` is mapped to: ``result.rid`` where the reference has contigs"""
+    if not many:
+        return names[0], lens[0]
+    rid = getattr(result, "rid", None)
+    if rid is None:
+        raise ValueError("the result has no rid: map the reads against an index with contigs (build_index_contigs)")
+    return names[int(rid[k])], lens[int(rid[k])]
+
+
 def sam_header(ref_name, ref_len):
-    """The header of a SAM file over one reference sequence."""
-    return "@HD\tVN:1.6\tSO:unsorted\n@SQ\tSN:%s\tLN:%d\n@PG\tID:mgl_amd\tPN:mgl_amd\n" % (ref_name, int(ref_len))
+    """The header of a SAM file over one reference sequence, or -- ``ref_name`` and ``ref_len`` as lists -- over its contigs, one @SQ
+    line each."""
+    names, lens, _ = _targets(ref_name, ref_len)
+    return "@HD\tVN:1.6\tSO:unsorted\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % x for x in zip(names, lens)) + "@PG\tID:mgl_amd\tPN:mgl_amd\n"
 
 
 def _oriented(seq, strand):
@@ -277,7 +300,9 @@ def write_sam(path, ref_name, ref_len, names, reads, quals, result, extended=Fal
     were given; ``quals``: their qualities as text (phred + 33), or None for ``*``.  A mapped read: FLAG 0 or 16, POS ref_beg + 1, the
     result's MAPQ, CIGAR = q_beg S, the core (the = / X form with ``extended``), (read length - q_end) S, SEQ the ORIENTED read (its
     reverse complement on strand 1, QUAL reversed with it), tags NM:i, MD:Z, AS:i.  An unmapped read: FLAG 4, ``*`` and 0, SEQ and
-    QUAL as given."""
+    QUAL as given.  ``ref_name`` and ``ref_len`` as lists (one entry per contig): RNAME is the contig ``result.rid`` names and POS counts
+    from its start, as ``ref_beg`` of a result mapped against contigs does."""
+    names_, lens_, many = _targets(ref_name, ref_len)
     with open(path, "wt") as f:
         f.write(sam_header(ref_name, ref_len))
         for k, (name, read) in enumerate(zip(names, reads)):
@@ -290,7 +315,7 @@ def write_sam(path, ref_name, ref_len, names, reads, quals, result, extended=Fal
             cigar = ("%dS" % qb if qb else "") + _core_cigar(result, k, extended) + ("%dS" % (len(read) - qe) if len(read) > qe else "")
             if qual is not None and strand:
                 qual = qual[::-1]
-            f.write("\t".join([name, "16" if strand else "0", ref_name, str(int(result.ref_beg[k]) + 1), str(int(result.mapq[k])), cigar, "*", "0", "0",
+            f.write("\t".join([name, "16" if strand else "0", _target_of(result, k, names_, lens_, many)[0], str(int(result.ref_beg[k]) + 1), str(int(result.mapq[k])), cigar, "*", "0", "0",
                                _oriented(read, strand).decode(), qual or "*", "NM:i:%d" % int(result.nm[k]), "MD:Z:" + bytes(result.md[k]).decode("latin-1"),
                                "AS:i:%d" % int(result.score[k])]) + "\n")
 
@@ -299,14 +324,17 @@ def write_paf(path, ref_name, ref_len, names, reads, result, extended=False):
     """One PAF line per MAPPED read from a DescribedMapResult: the twelve columns -- query name, length, start and end on the ORIGINAL
     strand ([ql - q_end, ql - q_beg) for strand 1), strand, target name, length, start, end, matching bases, block length, MAPQ --
     and the tags NM:i, AS:i and cg:Z: (the core CIGAR, without clips; the = / X form with ``extended``).  An unmapped read has no
-    line."""
+    line.  ``ref_name`` and ``ref_len`` as lists (one entry per contig): the target's name and length are those of the contig
+    ``result.rid`` names, start and end count from its start."""
+    names_, lens_, many = _targets(ref_name, ref_len)
     with open(path, "wt") as f:
         for k, (name, read) in enumerate(zip(names, reads)):
             if not _mapped(result, k):
                 continue
+            tname, tlen = _target_of(result, k, names_, lens_, many)
             ql, strand, qb, qe = len(read), int(result.strand[k]), int(result.q_beg[k]), int(result.q_end[k])
             lo, hi = (ql - qe, ql - qb) if strand else (qb, qe)
-            f.write("\t".join([name, str(ql), str(lo), str(hi), "-" if strand else "+", ref_name, str(int(ref_len)), str(int(result.ref_beg[k])),
+            f.write("\t".join([name, str(ql), str(lo), str(hi), "-" if strand else "+", tname, str(tlen), str(int(result.ref_beg[k])),
                                str(int(result.ref_end[k])), str(int(result.n_match[k])), str(int(result.block_len[k])), str(int(result.mapq[k])),
                                "NM:i:%d" % int(result.nm[k]), "AS:i:%d" % int(result.score[k]), "cg:Z:" + _core_cigar(result, k, extended)]) + "\n")
 

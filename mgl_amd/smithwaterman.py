@@ -47,14 +47,47 @@ DescribedMapResult = namedtuple("DescribedMapResult", "ref_beg ref_end strand sc
 AlignmentStats = namedtuple("AlignmentStats", "n_match n_mismatch n_ins n_del n_ins_runs n_del_runs md_len xcigar_len")
 RankedChain = namedtuple("RankedChain", "score strand n_anchors t_beg t_end q_beg q_end parent n_sub subsc mapq end_index")
 IndexInfo = namedtuple("IndexInfo", "ref_len entries bytes k w")
+ContigTable = namedtuple("ContigTable", "names starts lens")
+ContigTable.__doc__ = "the contigs of an Index: names (a list of str), starts and lens (int64 arrays) in the reference buffer's coordinates"
+# the list results of the mappers against an index with contigs: ref_beg / ref_end count from the start of contig ``rid`` (-1 and None
+# for an unmapped read), whose name is ``rname``
+ContigMapResult = namedtuple("ContigMapResult", MapResult._fields + ("rid", "rname"))
+ContigRankedMapResult = namedtuple("ContigRankedMapResult", RankedMapResult._fields + ("rid", "rname"))
+ContigDescribedMapResult = namedtuple("ContigDescribedMapResult", DescribedMapResult._fields + ("rid", "rname"))
 
 
 class Index:
     """A minimizer index of one reference on the device (mgl_sw_index, include/mgl_sw.h; ``MicrosoftSmithWaterman.build_index``
-    makes it).  It owns the native handle and keeps ``ref``, the reference's device tensor, which the index itself does not."""
+    makes it).  It owns the native handle and keeps ``ref``, the reference's device tensor, which the index itself does not.
+    ``contigs``: a ContigTable where ``build_index_contigs`` made it, None for an index of one sequence -- the mappers go through the
+    contig stages where there is one."""
 
-    def __init__(self, handle, ref):
-        self.handle, self.ref = handle, ref
+    def __init__(self, handle, ref, contigs=None, owner=None):
+        self.handle, self.ref, self.contigs, self._owner = handle, ref, contigs, owner
+
+    def get_contigs(self):
+        """mgl_sw_index_get_contigs -> (starts, lens) int64 arrays; an index of one sequence reports one contig [0, ref_len)"""
+        n = C.c_int64()
+        _check(_lib.lib().mgl_sw_index_get_contigs(self.handle, 0, None, None, C.byref(n)))
+        starts, lens = np.zeros(n.value, np.int64), np.zeros(n.value, np.int64)
+        _check(_lib.lib().mgl_sw_index_get_contigs(self.handle, n.value, starts.ctypes.data, lens.ctypes.data, C.byref(n)))
+        return starts, lens
+
+    def contig_of_device(self, t, l, out=None):
+        """mgl_sw_index_contig_of_batch_device on int32 device tensors: per anchor the contig that holds [t, t + l) whole, -1 where
+        none does (tests/contig_textbook.py); enqueued on the current stream, not synchronised.  -> group (int32, as ``t``), which
+        ``chain_anchors_device(group=...)`` takes; ``out``: a tensor to write into."""
+        import torch
+
+        ctx = self._owner._ensure()
+        total = int(t.numel())
+        if out is None:
+            out = torch.empty(total, dtype=torch.int32, device=t.device)
+        assert l.numel() >= total and out.numel() >= total
+        ptr = _ptrs(t.device)
+        _check(_lib.lib().mgl_sw_index_contig_of_batch_device(ctx, torch.cuda.current_stream(t.device).cuda_stream, self.handle, total, ptr(t), ptr(l),
+                                                              ptr(out)), ctx)
+        return out
 
     @property
     def info(self):
@@ -249,17 +282,40 @@ def _map_setup(reads, dev, slack, max_tl, stages):
     return n, packed, max_tl, max_ql, stride
 
 
-def _map_fields(n, stride, chosen, window, aln):
-    """The device tuples of a mapper, read back (the stream is done) -> (MapResult's six fields, ok, the alignments' records):
-    a read whose alignment has a status has zeros and an empty CIGAR, and the window's status where that refused the read."""
+def _contig_fields(index, window, ok):
+    """-> (rid [n] with -1 for a read that is not ``ok``, rname, the start of every read's contig) from a window tuple with rid"""
+    rid = np.where(ok, window[4].cpu().numpy(), -1).astype(np.int32)
+    return rid, [index.contigs.names[c] if c >= 0 else None for c in rid], np.where(rid >= 0, index.contigs.starts[np.maximum(rid, 0)], 0)
+
+
+def _contig_secondary(index, secondary):
+    """the ranked chains behind the first with their contig, found from ref_beg on the host: (ref_beg, ref_end, strand, score, parent,
+    rid), ref_beg and ref_end from that contig's start"""
+    starts = index.contigs.starts
+    out = []
+    for chains in secondary:
+        rids = [int(np.searchsorted(starts, c[0], side="right")) - 1 for c in chains]
+        out.append([(c[0] - int(starts[r]), c[1] - int(starts[r])) + tuple(c[2:]) + (r,) for c, r in zip(chains, rids)])
+    return out
+
+
+def _map_fields(n, stride, chosen, window, aln, index=None):
+    """The device tuples of a mapper, read back (the stream is done) -> (MapResult's six fields, ok, the alignments' records, the
+    contig fields): a read whose alignment has a status has zeros and an empty CIGAR, and the window's status where that refused the
+    read.  With an ``index`` that has contigs ref_beg and ref_end count from the start of the read's contig and the contig fields
+    are (rid, rname); otherwise they are ()."""
     rec, cg, ln, st = aln[0].cpu().numpy(), aln[4].cpu().numpy().reshape(n, stride), aln[5].cpu().numpy(), aln[6].cpu().numpy()
     t_start, wst = window[0].cpu().numpy(), window[3].cpu().numpy()
     ok = st == 0
+    contig = ()
+    if index is not None and index.contigs is not None:
+        rid, rname, origin = _contig_fields(index, window, ok)
+        t_start, contig = t_start - origin, (rid, rname)
     strand = chosen[0].cpu().numpy() if chosen is not None else np.zeros(n, np.int32)
     ln = np.where(ok, ln, 0).astype(np.int32)
     fields = (np.where(ok, t_start + rec[:, 1], 0), np.where(ok, t_start + rec[:, 2], 0), np.where(ok, strand, 0).astype(np.int32),
               np.where(ok, rec[:, 0], 0).astype(np.int32), CigarColumn(cg, ln), np.where(wst != 0, wst, st).astype(np.int32))
-    return fields, ok, rec
+    return fields, ok, rec, contig
 
 
 def _rank_fields(n, ranked):
@@ -540,14 +596,16 @@ class MicrosoftSmithWaterman:
         _check(rc, ctx)
         return out
 
-    def chain_anchors(self, t_lens, q_lens, candidates, max_pred=64, max_dist=5000, bw=500, pen_gap=38, pen_skip=0, max_cand=None, return_dp=False):
+    def chain_anchors(self, t_lens, q_lens, candidates, max_pred=64, max_dist=5000, bw=500, pen_gap=38, pen_skip=0, max_cand=None, return_dp=False,
+                      groups=None):
         """mgl_sw_chain_anchors_batch_device over lists: ``candidates[k]`` = a list of (t, q, l) for read k -- t_lens[k] and q_lens[k]
         are its window's and its query's length --, sorted by the caller (by target position) if the window of ``max_pred`` predecessors
         is to mean something.  ``max_dist``: one bound or (max_dist_t, max_dist_q).  The colinear chaining DP of
         tests/chain_dp_textbook.py and the best chain of every read.  NOT a reference function.  Returns ChainAnchorsResult: ``chains``
         (a list of lists of (t, q, l)), ``score`` and ``status`` arrays (a refused read has an empty chain; no exception for a read's
         status); with ``return_dp`` also f and pred of every candidate (int32 arrays in the order of the lists; what a refused read's
-        candidates hold is unspecified): (result, f, pred)."""
+        candidates hold is unspecified): (result, f, pred).  ``groups[k]``: a group per candidate of read k -- a candidate is chained
+        only to candidates of its own group, and one of group -1 to none (mgl_sw_chain_anchors_grouped_batch_device); None: no groups."""
         import torch
 
         dev = torch.device("cuda", self._device)
@@ -558,18 +616,21 @@ class MicrosoftSmithWaterman:
             max_cand = int(np.diff(start).max(initial=0))
         g = lambda x, dt: _upload(x, dev, dt)  # noqa: E731
         out = self.chain_anchors_device(g(t_lens, np.int32), g(q_lens, np.int32), g(start, np.int64), g(flat[:, 0], np.int32), g(flat[:, 1], np.int32),
-                                        g(flat[:, 2], np.int32), max_cand, max_pred, max_dist, bw, pen_gap, pen_skip, dp=return_dp)
+                                        g(flat[:, 2], np.int32), max_cand, max_pred, max_dist, bw, pen_gap, pen_skip, dp=return_dp,
+                                        group=None if groups is None else g([x for r in groups for x in r], np.int32))
         torch.cuda.synchronize(dev)
         cs, ct, cq, cl, score, f, pred, st = (None if x is None else x.cpu().numpy() for x in out)
         res = ChainAnchorsResult(_candidate_lists(cs, ct, cq, cl, n), score, st)
         return (res, f, pred) if return_dp else res
 
     def chain_anchors_device(self, t_len, q_len, cand_start, cand_t, cand_q, cand_len, max_cand, max_pred=64, max_dist=5000, bw=500, pen_gap=38,
-                             pen_skip=0, out=None, dp=False):
+                             pen_skip=0, out=None, dp=False, group=None):
         """The device-tensor form: torch tensors on this context's GPU (int32 lengths and candidates, int64 ``cand_start`` [n + 1]);
         enqueued on the current stream, not synchronised.  Returns (chain_start [n + 1] int64, chain_t, chain_q, chain_len [candidates],
         score [n], f or None, pred or None [candidates], status [n]) tensors -- f and pred with ``dp`` --; ``out``: such a tuple to
-        write into.  The first four are ``align_chain_device``'s anchor arguments as they are."""
+        write into.  The first four are ``align_chain_device``'s anchor arguments as they are.  ``group``: an int32 tensor, one entry
+        per candidate (``Index.contig_of_device`` makes it): mgl_sw_chain_anchors_grouped_batch_device, where a candidate is chained
+        only to candidates of its own group and one of group -1 to none (tests/contig_textbook.py); None: the entry without groups."""
         import torch
 
         ctx = self._ensure()
@@ -582,10 +643,14 @@ class MicrosoftSmithWaterman:
         cs, ct, cq, cl, score, f, pred, st = out
         dist_t, dist_q = (max_dist, max_dist) if np.isscalar(max_dist) else max_dist
         ptr = _ptrs(dev)
-        rc = _lib.lib().mgl_sw_chain_anchors_batch_device(
-            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(t_len), ptr(q_len), ptr(cand_start), ptr(cand_t), ptr(cand_q), ptr(cand_len), total,
-            int(max_cand), int(max_pred), int(dist_t), int(dist_q), int(bw), int(pen_gap), int(pen_skip), ptr(cs), ptr(ct), ptr(cq), ptr(cl), ptr(score),
-            ptr(f), ptr(pred), ptr(st))
+        head = (ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(t_len), ptr(q_len), ptr(cand_start), ptr(cand_t), ptr(cand_q), ptr(cand_len))
+        tail = (total, int(max_cand), int(max_pred), int(dist_t), int(dist_q), int(bw), int(pen_gap), int(pen_skip), ptr(cs), ptr(ct), ptr(cq), ptr(cl),
+                ptr(score), ptr(f), ptr(pred), ptr(st))
+        if group is None:
+            rc = _lib.lib().mgl_sw_chain_anchors_batch_device(*head, *tail)
+        else:
+            assert group.numel() >= total
+            rc = _lib.lib().mgl_sw_chain_anchors_grouped_batch_device(*head, ptr(group), *tail)
         _check(rc, ctx)
         return out
 
@@ -753,7 +818,61 @@ class MicrosoftSmithWaterman:
         rc = _lib.lib().mgl_sw_index_build_device(ctx, torch.cuda.current_stream(dev).cuda_stream, ref.data_ptr() or None, int(ref.numel()), int(k), int(w),
                                                   C.byref(handle))
         _check(rc, ctx)
-        return Index(handle, ref)
+        return Index(handle, ref, None, self)
+
+    def build_index_contigs(self, contigs, k=15, w=10, gap=1):
+        """mgl_sw_index_build_contigs_device over a list of (name, bytes): the contigs laid into one buffer with ``gap`` >= 1 bytes
+        of ``N`` between two of them, that buffer indexed as ``build_index`` does, and the table kept (DESIGN.md section 9m,
+        tests/contig_textbook.py).  NOT a reference function.  Returns an ``Index`` whose ``contigs`` is the ContigTable: the
+        mappers then chain and place a read inside ONE contig and report positions from that contig's start."""
+        assert gap >= 1 and len(contigs) >= 1
+        names, seqs = [n for n, _ in contigs], [bytes(s) for _, s in contigs]
+        starts = np.cumsum([0] + [len(s) + gap for s in seqs[:-1]]).astype(np.int64)
+        return self.build_index_contigs_device((b"N" * gap).join(seqs), starts, [len(s) for s in seqs], names, k, w)
+
+    def build_index_contigs_device(self, ref, starts, lens, names=None, k=15, w=10):
+        """The variant for a buffer that is laid out already: ``ref`` a uint8 tensor on this context's GPU (or bytes, copied there),
+        ``starts`` and ``lens`` its contigs (host integers; include/mgl_sw.h has the rules: they and the gaps tile the buffer, and
+        a gap holds no base), ``names`` default to contig0 ...  Synchronises the current stream."""
+        import torch
+
+        ctx = self._ensure()
+        dev = torch.device("cuda", self._device)
+        if not isinstance(ref, torch.Tensor):
+            ref = torch.from_numpy(np.frombuffer(bytes(ref), dtype=np.uint8).copy()).to(dev)
+        assert ref.dtype == torch.uint8 and ref.is_contiguous()
+        starts, lens = np.ascontiguousarray(starts, dtype=np.int64), np.ascontiguousarray(lens, dtype=np.int64)
+        assert starts.ndim == lens.ndim == 1 and len(starts) == len(lens)
+        names = ["contig%d" % c for c in range(len(starts))] if names is None else [str(x) for x in names]
+        assert len(names) == len(starts)
+        handle = C.c_void_p()
+        rc = _lib.lib().mgl_sw_index_build_contigs_device(ctx, torch.cuda.current_stream(dev).cuda_stream, ref.data_ptr() or None, int(ref.numel()),
+                                                          starts.ctypes.data, lens.ctypes.data, len(starts), int(k), int(w), C.byref(handle))
+        _check(rc, ctx)
+        return Index(handle, ref, ContigTable(names, starts, lens), self)
+
+    def locate_window_contigs_device(self, index, q_len, anchor_start, anchor_t, anchor_q, anchor_len, slack, max_tl, out=None, in_place=False):
+        """mgl_sw_locate_window_contigs_batch_device on device tensors: ``locate_window_device`` with the window kept inside the contig
+        of the read's first anchor, and a read whose anchors lie in two contigs (or in none) refused (tests/contig_textbook.py).
+        Returns (t_start [n] int64 -- in the BUFFER's coordinates --, t_len [n], anchor_t, status [n], rid [n] int32: the read's contig,
+        -1 for an unmapped or a refused read); ``out``: such a tuple (its status may be None).  An index of one sequence is one contig."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(q_len.numel())
+        total = int(anchor_t.numel())
+        dev = q_len.device
+        if out is None:
+            new = _alloc(dev)
+            out = (new(n, torch.int64), new(n), anchor_t if in_place else new(total), new(n), new(n))
+        ts, tl, at, st, rid = out
+        assert anchor_start.numel() >= n + 1 and min(anchor_q.numel(), anchor_len.numel(), at.numel()) >= total and min(ts.numel(), tl.numel(), rid.numel()) >= n
+        ptr = _ptrs(dev)
+        rc = _lib.lib().mgl_sw_locate_window_contigs_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, index.handle, ptr(q_len), ptr(anchor_start), ptr(anchor_t), ptr(anchor_q), ptr(anchor_len),
+            total, int(slack), int(max_tl), ptr(ts), ptr(tl), ptr(at), ptr(rid), ptr(st))
+        _check(rc, ctx)
+        return out
 
     def seed_index(self, index, queries, strands=2, max_occ=8, max_occ_ref=64, merge=True, max_cand=4096):
         """mgl_sw_seed_index_batch_device over a list of byte strings: ``seed_strands`` with the whole indexed reference for every
@@ -826,12 +945,16 @@ class MicrosoftSmithWaterman:
         choice's tuple or None, the window's tuple, the alignment's tuple).  The alignment's t_beg / t_end are relative to the read's
         window: on the reference it spans [t_start + t_beg, t_start + t_end); q and the CIGAR are the ORIENTED read's, as in
         ``align_reads_strands_device``.  A read without a chain (unmapped) has t_len 0 and is status MGL_SW_ERR_BAD_ARG in the
-        alignment's tuple."""
+        alignment's tuple.  Where the index has contigs (``build_index_contigs``) the candidates get their contig
+        (``Index.contig_of_device``), the chain stage runs grouped by it and the window comes from ``locate_window_contigs_device``:
+        its tuple then has rid as a fifth element, and t_start still counts from the start of the buffer."""
         seeds = self.seed_index_device(index, queries, q_start, q_len, strands, max_occ, max_occ_ref, merge, max_cand, cand_capacity, out=seed_out)
-        chain = self.chain_anchors_device(seeds[4], seeds[5], *seeds[:4], max_cand, max_pred, max_dist, bw, pen_gap, pen_skip, out=chain_out)
+        group = index.contig_of_device(seeds[1], seeds[3]) if index.contigs is not None else None
+        chain = self.chain_anchors_device(seeds[4], seeds[5], *seeds[:4], max_cand, max_pred, max_dist, bw, pen_gap, pen_skip, out=chain_out, group=group)
         chosen = self.select_strand_device(queries, q_start, q_len, *chain[:5], out=select_out) if strands == 2 else None
         oriented, anchors = (chosen[1], chosen[2:6]) if chosen is not None else (queries, chain[:4])
-        window = self.locate_window_device(index, q_len, *anchors, slack, max_tl, out=locate_out)
+        locate = self.locate_window_contigs_device if index.contigs is not None else self.locate_window_device
+        window = locate(index, q_len, *anchors, slack, max_tl, out=locate_out)
         dist_t, dist_q = (max_dist, max_dist) if np.isscalar(max_dist) else max_dist
         aln = self.align_chain_device(index.ref, window[0], window[1], oriented, q_start, q_len, anchors[0], window[2], anchors[2], anchors[3], max_tl,
                                       max_ql, dist_t, dist_q, band, zdrop, parameters, **align)
@@ -842,7 +965,9 @@ class MicrosoftSmithWaterman:
         either side; ``stages``: the further arguments of ``map_reads_device``.  Returns MapResult, per read: ``ref_beg`` and
         ``ref_end`` (the alignment spans [ref_beg, ref_end) of the reference), ``strand``, ``score``, ``cigars`` (of the oriented
         read) and ``status`` (0; the window's status where it refused the read; MGL_SW_ERR_BAD_ARG for an unmapped read -- such a
-        read's other fields are 0 and its CIGAR empty; no exception for a read's status)."""
+        read's other fields are 0 and its CIGAR empty; no exception for a read's status).  Against an index with contigs
+        (``build_index_contigs``) it returns ContigMapResult: the same fields with ``ref_beg`` and ``ref_end`` counted from the start
+        of the read's contig, and ``rid`` (-1: unmapped) and ``rname``."""
         import torch
 
         dev = torch.device("cuda", self._device)
@@ -850,7 +975,8 @@ class MicrosoftSmithWaterman:
         _, _, chosen, window, aln = self.map_reads_device(index, *packed, max_tl, max_ql, band, zdrop, parameters, slack, strands, cigar_stride=stride,
                                                           **stages)
         torch.cuda.synchronize(dev)
-        return MapResult(*_map_fields(n, stride, chosen, window, aln)[0])
+        fields, _, _, contig = _map_fields(n, stride, chosen, window, aln, index)
+        return ContigMapResult(*fields, *contig) if contig else MapResult(*fields)
 
     def rank_chains(self, row_q_lens, candidates, f, pred, row_status=None, strands=2, max_chains=4, min_score=40, min_cnt=3, mask_level=128,
                     max_cand=None, return_anchors=False):
@@ -948,7 +1074,11 @@ class MicrosoftSmithWaterman:
         _, _, chosen, window, aln, ranked = self.map_reads_ranked_device(index, *packed, max_tl, max_ql, band, zdrop, parameters, strands=strands,
                                                                          slack=slack, cigar_stride=stride, **stages)
         torch.cuda.synchronize(dev)
-        return RankedMapResult(*_map_fields(n, stride, chosen, window, aln)[0], *_rank_fields(n, ranked))
+        fields, _, _, contig = _map_fields(n, stride, chosen, window, aln, index)
+        mapq, nc, secondary = _rank_fields(n, ranked)
+        if contig:
+            return ContigRankedMapResult(*fields, mapq, nc, _contig_secondary(index, secondary), *contig)
+        return RankedMapResult(*fields, mapq, nc, secondary)
 
     def describe_device(self, targets, t_start, t_len, queries, q_start, q_len, aln, cigar, cigar_stride, cigar_len, status_in=None, md_stride=None,
                         xcigar_stride=None, binary_cigar=False, md=True, xcigar=True, out=None):
@@ -1050,7 +1180,7 @@ class MicrosoftSmithWaterman:
         _, _, chosen, window, aln, ranked, desc = self.map_reads_described_device(index, *packed, max_tl, max_ql, band, zdrop, parameters, strands=strands,
                                                                                   slack=slack, cigar_stride=stride, xcigar=bool(extended), **stages)
         torch.cuda.synchronize(dev)
-        fields, ok, rec = _map_fields(n, stride, chosen, window, aln)
+        fields, ok, rec, contig = _map_fields(n, stride, chosen, window, aln, index)
         stats, dst = desc[0].cpu().numpy().reshape(n, 8), desc[3].cpu().numpy()
         over = np.flatnonzero(ok & (dst != 0))
         if over.size:  # the alignment stands and its description does not: a text beyond its stride
@@ -1059,8 +1189,12 @@ class MicrosoftSmithWaterman:
         mds = [md[p, :stats[p, 6]].tobytes() for p in range(n)]
         nm = (stats[:, 1] + stats[:, 2] + stats[:, 3]).astype(np.int32)
         z = lambda x: np.where(ok, x, 0).astype(np.int32)  # noqa: E731
-        return DescribedMapResult(*fields, *_rank_fields(n, ranked), z(rec[:, 3]), z(rec[:, 4]), nm, stats[:, 0].astype(np.int32),
-                                  (stats[:, 0] + nm).astype(np.int32), mds, CigarColumn(desc[2].cpu().numpy().reshape(n, -1), stats[:, 7].astype(np.int32)) if extended else None)
+        mapq, nc, secondary = _rank_fields(n, ranked)
+        if contig:
+            secondary = _contig_secondary(index, secondary)
+        return (ContigDescribedMapResult if contig else DescribedMapResult)(
+            *fields, mapq, nc, secondary, z(rec[:, 3]), z(rec[:, 4]), nm, stats[:, 0].astype(np.int32), (stats[:, 0] + nm).astype(np.int32), mds,
+            CigarColumn(desc[2].cpu().numpy().reshape(n, -1), stats[:, 7].astype(np.int32)) if extended else None, *contig)
 
     def align_packed_2bit(self, target_bases, target_base_count, t_start, t_len, query_bases, query_base_count, q_start, q_len,
                           max_tl, max_ql, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,

@@ -195,6 +195,33 @@ def mapping_set(seed, count, length=10000, spacer=3000):
     return b"".join(parts), reads, truth
 
 
+def contig_cuts(count, truth, spacer, contigs):
+    """The ``contigs`` - 1 positions at which ``mapping_set``'s reference is cut into contigs, ascending: every one inside a spacer
+    between two reads (the outer spacers where there is one read), spread over them in order, evenly spaced inside a spacer.  The
+    byte AT a cut belongs to neither side: it is the gap."""
+    if contigs == 1:
+        return []
+    begins = [pos - spacer for pos, _, _ in truth] + [truth[-1][0] + truth[-1][1]]  # where the count + 1 spacers begin
+    usable = begins[1:count] if count > 1 else begins
+    per = [0] * len(usable)
+    for k in range(contigs - 1):
+        per[k * len(usable) // (contigs - 1)] += 1
+    assert 2 * max(per) < spacer, "the spacers do not hold that many cuts"
+    return [b + spacer * (j + 1) // (m + 1) for b, m in zip(usable, per) for j in range(m)]
+
+
+def contig_mapping_set(seed, count, length=10000, spacer=3000, contigs=2):
+    """``mapping_set(seed, count, length, spacer)``'s reference cut into ``contigs`` pieces inside its spacers (``contig_cuts``; the
+    byte at a cut is dropped: laid out again with one gap byte between two contigs, every base is where ``mapping_set`` has it).
+    -> (contigs as [(name, bytes)], reads, truth), truth[p] = (the contig of T_p, its position in that contig, len(T_p), the strand)."""
+    ref, reads, truth = mapping_set(seed, count, length, spacer)
+    assert spacer >= 3 and 1 <= contigs
+    edges = [-1] + contig_cuts(count, truth, spacer, contigs) + [len(ref)]
+    pieces = [("contig%d" % c, ref[a + 1:b]) for c, (a, b) in enumerate(zip(edges, edges[1:]))]
+    rid = [max(c for c in range(contigs) if edges[c] < pos) for pos, _, _ in truth]
+    return pieces, reads, [(c, pos - edges[c] - 1, n, s) for c, (pos, n, s) in zip(rid, truth)]
+
+
 def repeat_mapping_set(seed, count, length=10000, spacer=3000, copies=0, divergence=0.0):
     """``mapping_set(seed, count, length, spacer)`` on a reference with repeats: the windows of the first ``copies`` reads appended
     once more to the reference, each with its bases substituted (by another base) at rate ``divergence`` and followed by ``spacer``
