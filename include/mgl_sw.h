@@ -1021,6 +1021,89 @@ int mgl_sw_rank_chains_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, in
                                     int32_t *d_ranked_q_out, int32_t *d_ranked_len_out, int32_t *d_status_out);
 
 /*
+ * ONE ALIGNMENT JOB PER RANKED CHAIN (NOT a reference function; opt-in): behind mgl_sw_rank_chains_batch_device with its anchor outputs,
+ * in front of the window, alignment and describe stages, which take the jobs as their pairs.  Defined by tests/lines_textbook.py
+ * (expand_chains, oriented); DESIGN.md section 9n.  Read p is d_queries[d_q_start[p] .. + d_q_len[p]) of a buffer of query_bytes; it has
+ * d_n_chains[p] records at d_records[p * max_chains ..] and their anchors, one chain behind the other in rank order, at
+ * d_ranked_start[p] .. d_ranked_start[p + 1] (int64, n + 1) of d_ranked_t / _q / _len (total_anchors each), and optionally the rank
+ * stage's status d_rank_status[p].
+ * Every ranked chain c of a read gives one job, in rank order; with keep_secondary = 0 only the chains with parent == c do.  Jobs are
+ * numbered densely over the batch in read order: d_job_start_out (int64, n + 1), *d_n_jobs_out = d_job_start_out[n] (one int64 on the
+ * device).  mgl_sw_job: read, rank, strand, n_anchors, chain_score (the record's score), chain_parent, q_len, reserved (0).
+ * d_job_q_len_out[j] = q_len of the job's read; d_job_q_start_out[j] = q_start of the job's read + strand * query_bytes, an offset into
+ * d_oriented_out (2 * query_bytes): its first half gets Q_p at d_q_start[p] for every read with a strand-0 job, its second half rc(Q_p)
+ * at query_bytes + d_q_start[p] for every read with a strand-1 job (A <-> T, C <-> G, every other byte as it is, as
+ * mgl_sw_select_strand_batch_device complements); no byte of a read without such a job and no byte outside a read is written.
+ * d_job_anchor_start_out (int64, job_capacity + 1) is the prefix sum of the jobs' n_anchors and d_job_anchor_t_out / _q_out / _len_out
+ * (total_anchors each) hold the jobs' anchors one behind the other, copied: a CSR start array has no gaps, and the ranked arrays have
+ * them wherever a chain is skipped or a read refused.  Jobs at or beyond *d_n_jobs_out and below job_capacity are written EMPTY: read
+ * -1, every other field 0, q_start 0, q_len 0, no anchors; mgl_sw_locate_window_batch_device (ql < 1) and
+ * mgl_sw_align_chain_batch_device (a length below 1) refuse such a pair with MGL_SW_ERR_BAD_ARG, so the stages behind this one run
+ * over job_capacity pairs with no count read back.
+ * d_status_out (optional), per read, in this order: d_rank_status[p] where that is not 0 (nothing else of the read is read);
+ * MGL_SW_ERR_BAD_ARG for q_len < 1, a read that leaves [0, query_bytes), n_chains outside 0 .. max_chains, a record with strand
+ * outside 0 / 1 or n_anchors < 1, and a d_ranked_start range that descends, leaves [0, total_anchors] or is not the sum of the read's
+ * n_anchors; MGL_SW_ERR_NOMEM by the capacity rule, which is per read and greedy: in index order a read is kept iff the jobs kept so
+ * far and its own stay within job_capacity (and the anchors likewise within total_anchors, which only ranges that overlap can
+ * exceed); a read that is not kept changes nothing for the reads behind it.  A read with a status has no jobs.
+ * MGL_SW_ERR_BAD_ARG before any device work for a null required pointer (d_rank_status and d_status_out are optional), n outside
+ * [0, 2^29], max_chains outside 1 .. 16, job_capacity or total_anchors outside [0, 2^30], query_bytes < 0 or above 2^40,
+ * keep_secondary outside 0 / 1, and d_oriented_out overlapping d_queries; MGL_SW_ERR_DEVICE without a GPU; MGL_SW_ERR_NOMEM where the
+ * workspace limit does not hold 20 bytes per read.  n = 0 is MGL_SW_OK and writes *d_n_jobs_out = 0 and the empty jobs.
+ * Device work on `stream`, no synchronisation: sw_expand_count_kernel (a thread per read), sw_expand_scan_kernel (one block),
+ * sw_expand_pack_kernel (a wave per read) and sw_expand_orient_kernel (a workgroup per read and strand, 16 bytes a store between the
+ * unaligned ends).  No MGL_SW_KERNEL_* id: the timing record keeps its fill_kernel.
+ * LIMITS: max_chains <= 16; no hard clips: every job carries the whole read.
+ */
+typedef struct mgl_sw_job {
+    int32_t read, rank, strand, n_anchors, chain_score, chain_parent, q_len, reserved;
+} mgl_sw_job;
+
+int mgl_sw_expand_chains_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_queries, const int64_t *d_q_start,
+                                      const int32_t *d_q_len, int64_t query_bytes, const int32_t *d_rank_status, const int32_t *d_n_chains,
+                                      const mgl_sw_ranked_chain *d_records, int max_chains, const int64_t *d_ranked_start,
+                                      const int32_t *d_ranked_t, const int32_t *d_ranked_q, const int32_t *d_ranked_len, int64_t total_anchors,
+                                      int keep_secondary, int64_t job_capacity, int64_t *d_n_jobs_out, int64_t *d_job_start_out,
+                                      mgl_sw_job *d_jobs_out, int64_t *d_job_q_start_out, int32_t *d_job_q_len_out,
+                                      int64_t *d_job_anchor_start_out, int32_t *d_job_anchor_t_out, int32_t *d_job_anchor_q_out,
+                                      int32_t *d_job_anchor_len_out, uint8_t *d_oriented_out, int32_t *d_status_out);
+
+/*
+ * THE LINES OF A READ (NOT a reference function; opt-in): behind mgl_sw_align_chain_batch_device over the jobs of
+ * mgl_sw_expand_chains_batch_device.  Defined by tests/lines_textbook.py (classify_alignments); DESIGN.md section 9n.  Read p has the
+ * jobs d_job_start[p] .. d_job_start[p + 1] (at most 16); job j has its record d_jobs[j], its alignment d_aln[j] (of which score, q_beg
+ * and q_end are read) and d_aln_status[j]; nothing of the alignment of a job with a non-zero status is read.
+ * A job is live iff its status is 0, q_end > q_beg and score >= 1.  A read's live jobs ordered by (alignment score descending, rank
+ * ascending, job index ascending) are its lines.  A line's interval on the forward read is [q_beg, q_end) on strand 0 and
+ * [q_len - q_end, q_len - q_beg) on strand 1.  Parents are found as mgl_sw_rank_chains_batch_device finds them, on these intervals in
+ * line order, with mask_level / 256 of the shorter.  flag: 0x10 on strand 1; the first line is the primary; another line that is its
+ * own parent gets 0x800 (supplementary); a line with a parent gets 0x100 (secondary).  mapq (0 .. 60) of a line that is its own
+ * parent comes from its alignment score, its chain score, its anchors, the number of its secondaries (n_sub), the best alignment
+ * score among them (subsc) and that secondary's chain score, in 64-bit integers: minimap2's DP branch, no parity claimed.  A secondary
+ * line has mapq, n_sub and subsc 0.
+ * d_lines_out[j] (mgl_sw_line), per JOB index so that it lines up with the alignment's, the CIGAR's and the describe stage's rows:
+ * order (the line's place among the read's lines), flag, mapq, parent (a job index; the line's own where it is its own parent),
+ * n_sub, subsc, fwd_q_beg, fwd_q_end.  A job that is not live has (-1, 0, 0, -1, 0, 0, 0, 0).  Only the jobs of accepted reads get a
+ * record: the empty jobs behind the last read's do not.  d_n_lines_out[p]; d_primary_job_out[p]: the job of line 0, -1 for an
+ * unmapped read.
+ * d_status_out (optional), per read: MGL_SW_ERR_BAD_ARG for a d_job_start range that descends, leaves [0, job_capacity] or is longer
+ * than 16, and for a job in it whose `read` is not p; such a read has n_lines 0, primary_job -1 and no record written.
+ * MGL_SW_ERR_BAD_ARG before any device work for a null required pointer, n outside [0, 2^29], job_capacity outside [0, 2^30], match
+ * or min_score < 1 and mask_level outside 1 .. 256; MGL_SW_ERR_DEVICE without a GPU.  n = 0 is MGL_SW_OK.
+ * Device work on `stream`, no synchronisation, no workspace, no LDS: sw_classify_kernel, a quarter wave per read.  No MGL_SW_KERNEL_*
+ * id: the timing record keeps its fill_kernel.
+ * LIMITS: 16 jobs a read; one window per chain; no supplementary-specific chaining of a clipped remainder.
+ */
+typedef struct mgl_sw_line {
+    int32_t order, flag, mapq, parent, n_sub, subsc, fwd_q_beg, fwd_q_end;
+} mgl_sw_line;
+
+int mgl_sw_classify_alignments_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const int64_t *d_job_start, const mgl_sw_job *d_jobs,
+                                            int64_t job_capacity, const mgl_sw_chain_alignment *d_aln, const int32_t *d_aln_status, int match,
+                                            int min_score, int mask_level, mgl_sw_line *d_lines_out, int32_t *d_n_lines_out,
+                                            int32_t *d_primary_job_out, int32_t *d_status_out);
+
+/*
  * DESCRIBING ALIGNMENTS (NOT a reference function; opt-in): behind mgl_sw_align_chain_batch_device or
  * mgl_sw_extend_seed_batch_device, on the same stream, with no copy and no synchronisation in between.  What a SAM or PAF record
  * needs beyond the M / I / D CIGAR: matches, mismatches, inserted and deleted bases and runs, the MD text and the extended (= / X)

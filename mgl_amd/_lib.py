@@ -39,7 +39,7 @@ SYMBOLS = (
     "mgl_sw_index_export_device", "mgl_sw_seed_index_batch_device", "mgl_sw_locate_window_batch_device",
     "mgl_sw_rank_chains_batch_device", "mgl_sw_describe_alignments_batch_device", "mgl_sw_index_build_contigs_device",
     "mgl_sw_index_get_contigs", "mgl_sw_index_contig_of_batch_device", "mgl_sw_chain_anchors_grouped_batch_device",
-    "mgl_sw_locate_window_contigs_batch_device",
+    "mgl_sw_locate_window_contigs_batch_device", "mgl_sw_expand_chains_batch_device", "mgl_sw_classify_alignments_batch_device",
 )
 # MGL_SW_VERSION of the include/mgl_sw.h this mirror was written against: the structs below (Plan, Timing) are that header's, and the
 # library writes sizeof(ITS struct) through the pointers it is given -- so a library of another version is refused at load time
@@ -79,6 +79,16 @@ class IndexInfo(C.Structure):
 class RankedChain(C.Structure):
     """mgl_sw_ranked_chain: one ranked chain of a read (mgl_sw_rank_chains_batch_device)."""
     _fields_ = [(n, C.c_int32) for n in ("score", "strand", "n_anchors", "t_beg", "t_end", "q_beg", "q_end", "parent", "n_sub", "subsc", "mapq", "end_index")]
+
+
+class Job(C.Structure):
+    """mgl_sw_job: one alignment job, a ranked chain of a read (mgl_sw_expand_chains_batch_device)."""
+    _fields_ = [(n, C.c_int32) for n in ("read", "rank", "strand", "n_anchors", "chain_score", "chain_parent", "q_len", "reserved")]
+
+
+class Line(C.Structure):
+    """mgl_sw_line: what a job's alignment is among the lines of its read (mgl_sw_classify_alignments_batch_device)."""
+    _fields_ = [(n, C.c_int32) for n in ("order", "flag", "mapq", "parent", "n_sub", "subsc", "fwd_q_beg", "fwd_q_end")]
 
 
 class AlignmentStats(C.Structure):
@@ -222,6 +232,9 @@ def lib():
     L.mgl_sw_rank_chains_batch_device.argtypes = [vp, vp, C.c_int64, C.c_int, vp, vp, vp, vp, vp, C.c_int64, vp, vp, vp] + [C.c_int] * 5 + [vp] * 7
     L.mgl_sw_describe_alignments_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp,
                                                           C.c_int]
+    L.mgl_sw_expand_chains_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int,
+                                                    C.c_int64] + [vp] * 11
+    L.mgl_sw_classify_alignments_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 4
     L.mgl_sw_backtrack_matrix.argtypes = [cp, C.c_int, cp, C.c_int] + [C.c_int] * 5 + [i32p, C.POINTER(Score)]
     L.mgl_sw_cigar_from_backtrack.argtypes = [i32p, C.c_int, C.c_int, C.c_int, C.POINTER(Score), cp, C.c_int,
                                               C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -339,6 +339,65 @@ def write_paf(path, ref_name, ref_len, names, reads, result, extended=False):
                                "NM:i:%d" % int(result.nm[k]), "AS:i:%d" % int(result.score[k]), "cg:Z:" + _core_cigar(result, k, extended)]) + "\n")
 
 
+def _line_cigar(line, ql, extended):
+    """a line's CIGAR with its soft clips, over the oriented read"""
+    if extended and line.xcigar is None:
+        raise ValueError("the result has no extended CIGARs: map_reads_all(..., extended=True)")
+    core = line.xcigar if extended else line.cigar
+    return ("%dS" % line.q_beg if line.q_beg else "") + core + ("%dS" % (ql - line.q_end) if ql > line.q_end else "")
+
+
+def _line_target(line, names, lens, many):
+    if not many:
+        return names[0], lens[0]
+    if line.rid is None:
+        raise ValueError("the result has no rid: map the reads against an index with contigs (build_index_contigs)")
+    return names[int(line.rid)], lens[int(line.rid)]
+
+
+def write_sam_all(path, ref_name, ref_len, names, reads, quals, result, extended=False):
+    """One SAM line per Line of an AllMapResult (MicrosoftSmithWaterman.map_reads_all), in line order.  FLAG as classified: 0x10 on
+    strand 1, 0x100 on a secondary and 0x800 on a supplementary line.  Every line carries the whole ORIENTED read (no hard clips): CIGAR
+    = q_beg S, the core (the = / X form with ``extended``), (read length - q_end) S; SEQ its reverse complement on strand 1 and QUAL
+    reversed with it.  Tags NM:i, MD:Z, AS:i and tp:A:P (tp:A:S on a secondary line); on each non-secondary line of a read that has
+    at least two of them SA:Z: lists the OTHER non-secondary lines in line order, each as rname,pos,+|-,CIGAR with clips,mapq,NM;.
+    A read without lines is written as ``write_sam`` writes an unmapped read.  ``ref_name`` and ``ref_len`` as in ``write_sam``."""
+    names_, lens_, many = _targets(ref_name, ref_len)
+    with open(path, "wt") as f:
+        f.write(sam_header(ref_name, ref_len))
+        for k, (name, read) in enumerate(zip(names, reads)):
+            read = bytes(read)
+            qual = None if quals is None or quals[k] is None else (quals[k] if isinstance(quals[k], str) else bytes(quals[k]).decode())
+            lines = result.lines[k]
+            if not lines:
+                f.write("\t".join([name, "4", "*", "0", "0", "*", "*", "0", "0", read.decode(), qual or "*"]) + "\n")
+                continue
+            chief = [ln for ln in lines if not ln.flag & 0x100]
+            sa = ["%s,%d,%s,%s,%d,%d;" % (_line_target(ln, names_, lens_, many)[0], ln.ref_beg + 1, "-" if ln.strand else "+", _line_cigar(ln, len(read), extended),
+                                          ln.mapq, ln.nm) for ln in chief]
+            for ln in lines:
+                tags = ["NM:i:%d" % ln.nm, "MD:Z:" + bytes(ln.md).decode("latin-1"), "AS:i:%d" % ln.score, "tp:A:S" if ln.flag & 0x100 else "tp:A:P"]
+                if not ln.flag & 0x100 and len(chief) >= 2:
+                    tags.append("SA:Z:" + "".join(s for other, s in zip(chief, sa) if other is not ln))
+                f.write("\t".join([name, str(ln.flag), _line_target(ln, names_, lens_, many)[0], str(ln.ref_beg + 1), str(ln.mapq), _line_cigar(ln, len(read), extended),
+                                   "*", "0", "0", _oriented(read, ln.strand).decode(), (qual[::-1] if ln.strand else qual) if qual is not None else "*"] + tags) + "\n")
+
+
+def write_paf_all(path, ref_name, ref_len, names, reads, result, extended=False):
+    """One PAF line per Line of an AllMapResult, in line order: ``write_paf``'s twelve columns and tags, and tp:A:P or tp:A:S
+    (secondary).  A read without lines has no line."""
+    names_, lens_, many = _targets(ref_name, ref_len)
+    with open(path, "wt") as f:
+        for k, (name, read) in enumerate(zip(names, reads)):
+            for ln in result.lines[k]:
+                tname, tlen = _line_target(ln, names_, lens_, many)
+                ql = len(read)
+                lo, hi = (ql - ln.q_end, ql - ln.q_beg) if ln.strand else (ln.q_beg, ln.q_end)
+                f.write("\t".join([name, str(ql), str(lo), str(hi), "-" if ln.strand else "+", tname, str(tlen), str(ln.ref_beg), str(ln.ref_end), str(ln.n_match),
+                                   str(ln.block_len), str(ln.mapq), "NM:i:%d" % ln.nm, "AS:i:%d" % ln.score, "tp:A:S" if ln.flag & 0x100 else "tp:A:P",
+                                   "cg:Z:" + (ln.xcigar if extended else ln.cigar)]) + "\n")
+
+
 def read_sam(path):
     """A small SAM reader: (header text, [(reference name, length)], [BamRecord]) as ``read_bam`` gives them -- ``pos`` 0-based (-1
     for ``*``), ``cigar`` a list of (len, op), ``seq`` ASCII bytes, ``qual`` raw phred bytes (empty for ``*``), ``tags`` with i / f

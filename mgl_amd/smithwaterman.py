@@ -46,6 +46,8 @@ DescribedMapResult = namedtuple("DescribedMapResult", "ref_beg ref_end strand sc
                                 "xcigars")
 AlignmentStats = namedtuple("AlignmentStats", "n_match n_mismatch n_ins n_del n_ins_runs n_del_runs md_len xcigar_len")
 RankedChain = namedtuple("RankedChain", "score strand n_anchors t_beg t_end q_beg q_end parent n_sub subsc mapq end_index")
+Line = namedtuple("Line", "ref_beg ref_end strand score cigar q_beg q_end flag mapq parent nm n_match block_len md xcigar rid rname status")
+AllMapResult = namedtuple("AllMapResult", "n_lines lines")
 IndexInfo = namedtuple("IndexInfo", "ref_len entries bytes k w")
 ContigTable = namedtuple("ContigTable", "names starts lens")
 ContigTable.__doc__ = "the contigs of an Index: names (a list of str), starts and lens (int64 arrays) in the reference buffer's coordinates"
@@ -1035,6 +1037,154 @@ class MicrosoftSmithWaterman:
             ptr(rt), ptr(rq), ptr(rl), ptr(st))
         _check(rc, ctx)
         return out
+
+    def expand_chains_device(self, queries, q_start, q_len, rank_status, n_chains, records, ranked_start, ranked_t, ranked_q, ranked_len, max_chains=4,
+                             keep_secondary=True, job_capacity=None, out=None):
+        """mgl_sw_expand_chains_batch_device on device tensors: the reads (uint8 ``queries``, int64 ``q_start``, int32 ``q_len``) and
+        what ``rank_chains_device(anchors=True)`` wrote for them (its status may be None) -> one alignment job per ranked chain
+        (tests/lines_textbook.py); enqueued on the current stream, not synchronised.  ``job_capacity`` defaults to n * max_chains.
+        Returns (n_jobs [1] int64, job_start [n + 1] int64, jobs [job_capacity, 8] int32 -- mgl_sw_job's fields --, job_q_start
+        [job_capacity] int64, job_q_len [job_capacity] int32, job_anchor_start [job_capacity + 1] int64, job_anchor_t, job_anchor_q,
+        job_anchor_len [as ranked_t] int32, oriented [2 * queries.numel()] uint8, status [n] int32) tensors; ``out``: such a tuple to
+        write into (its status may be None).  Jobs at or beyond n_jobs are empty (read -1, q_len 0): the stages behind this one run
+        over all job_capacity of them and refuse those."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(q_start.numel())
+        total, qbytes = int(ranked_t.numel()), int(queries.numel())
+        dev = queries.device
+        if job_capacity is None:
+            job_capacity = n * max(int(max_chains), 0)
+        cap = int(job_capacity)
+        if out is None:
+            new = _alloc(dev)
+            c = max(cap, 0)
+            out = (new(1, torch.int64), new(n + 1, torch.int64), new((c, 8)), new(c, torch.int64), new(c), new(c + 1, torch.int64), new(total), new(total),
+                   new(total), new(2 * qbytes, torch.uint8), new(n))
+        nj, js, jobs, jqs, jql, jas, jat, jaq, jal, ori, st = out
+        assert q_len.numel() >= n and n_chains.numel() >= n and records.numel() >= n * max_chains * 12 and ranked_start.numel() >= n + 1
+        assert min(ranked_q.numel(), ranked_len.numel(), jat.numel(), jaq.numel(), jal.numel()) >= total
+        assert js.numel() >= n + 1 and jobs.numel() >= 8 * cap and min(jqs.numel(), jql.numel()) >= cap and jas.numel() >= cap + 1 and ori.numel() >= 2 * qbytes
+        ptr = _ptrs(dev)
+        rc = _lib.lib().mgl_sw_expand_chains_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(queries), ptr(q_start), ptr(q_len), qbytes, ptr(rank_status), ptr(n_chains), ptr(records),
+            int(max_chains), ptr(ranked_start), ptr(ranked_t), ptr(ranked_q), ptr(ranked_len), total, int(bool(keep_secondary)), cap, ptr(nj), ptr(js),
+            ptr(jobs), ptr(jqs), ptr(jql), ptr(jas), ptr(jat), ptr(jaq), ptr(jal), ptr(ori), ptr(st))
+        _check(rc, ctx)
+        return out
+
+    def classify_alignments_device(self, job_start, jobs, aln, aln_status, match=None, min_score=40, mask_level=128, out=None):
+        """mgl_sw_classify_alignments_batch_device on device tensors: ``expand_chains_device``'s job_start [n + 1] and jobs
+        [job_capacity, 8] and ``align_chain_device``'s records [job_capacity, 8] and status over those jobs -> the lines of every read
+        (tests/lines_textbook.py); enqueued on the current stream, not synchronised.  ``match`` defaults to GATK_PARAMETERS'.  Returns
+        (lines [job_capacity, 8] int32 -- mgl_sw_line's fields, per job; only the jobs of accepted reads are written --, n_lines [n],
+        primary_job [n], status [n]) tensors; ``out``: such a tuple to write into (its status may be None)."""
+        ctx = self._ensure()
+        n = int(job_start.numel()) - 1
+        cap = int(jobs.numel()) // 8
+        dev = jobs.device
+        if match is None:
+            match = GATK_PARAMETERS.match
+        if out is None:
+            new = _alloc(dev)
+            out = (new((cap, 8)), new(max(n, 0)), new(max(n, 0)), new(max(n, 0)))
+        lines, nl, pj, st = out
+        assert aln.numel() >= 8 * cap and aln_status.numel() >= cap and lines.numel() >= 8 * cap and min(nl.numel(), pj.numel()) >= n
+        import torch
+
+        ptr = _ptrs(dev)
+        rc = _lib.lib().mgl_sw_classify_alignments_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(job_start), ptr(jobs), cap, ptr(aln), ptr(aln_status), int(match), int(min_score),
+            int(mask_level), ptr(lines), ptr(nl), ptr(pj), ptr(st))
+        _check(rc, ctx)
+        return out
+
+    def map_reads_all_device(self, index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters=GATK_PARAMETERS, slack=200, strands=2, max_occ=8,
+                             max_occ_ref=64, merge=True, max_cand=4096, cand_capacity=None, max_pred=64, max_dist=5000, bw=500, pen_gap=38, pen_skip=0,
+                             max_chains=4, min_score=40, min_cnt=3, mask_level=128, keep_secondary=True, job_capacity=None, md_stride=None,
+                             xcigar_stride=None, xcigar=True, **align):
+        """Reads in, EVERY ranked chain aligned and classified, on the current stream with nothing read back and nothing synchronised:
+        ``seed_index_device`` -> (``Index.contig_of_device`` where the index has contigs) -> ``chain_anchors_device`` with f and pred
+        -> ``rank_chains_device(anchors=True)`` -> ``expand_chains_device`` -> ``locate_window_device`` /
+        ``locate_window_contigs_device`` over the JOBS -> ``align_chain_device`` on the index's reference and the oriented buffer ->
+        ``describe_device`` -> ``classify_alignments_device``.  ``job_capacity`` defaults to n * max_chains; the stages behind the
+        expansion run over all of them and refuse the empty ones (status MGL_SW_ERR_BAD_ARG).  ``align``: the further arguments of
+        ``align_chain_device``.  Returns the stages' tuples: (seeds, chain, ranked, jobs, window, aln, described, lines).  Rows of
+        window, aln and described are per job; a line's t_beg / t_end are relative to its job's window, its q and CIGAR those of the
+        job's strand's oriented read.  Split reads want ``to_query_end=False`` or a Z-drop: an extension to the query's end aligns
+        through a breakpoint."""
+        import torch
+
+        n = int(q_start.numel())
+        dev = queries.device
+        binary = bool(align.get("binary_cigar", False))
+        if align.get("cigar_stride") is None:
+            align["cigar_stride"] = _default_stride(max_tl, max_ql, binary)
+        stride = int(align["cigar_stride"])
+        rows = max(int(strands), 0) * n
+        total = cand_capacity if cand_capacity is not None else min(rows * int(max_cand), 1 << 30)
+        new = _alloc(dev)
+        chain_out = (new(rows + 1, torch.int64), new(total), new(total), new(total), new(rows), new(total), new(total), new(rows))
+        seeds = self.seed_index_device(index, queries, q_start, q_len, strands, max_occ, max_occ_ref, merge, max_cand, cand_capacity)
+        group = index.contig_of_device(seeds[1], seeds[3]) if index.contigs is not None else None
+        chain = self.chain_anchors_device(seeds[4], seeds[5], *seeds[:4], max_cand, max_pred, max_dist, bw, pen_gap, pen_skip, out=chain_out, group=group)
+        ranked = self.rank_chains_device(seeds[5], *seeds[:4], chain[5], chain[6], chain[7], strands, max_cand, max_chains, min_score, min_cnt, mask_level,
+                                         anchors=True)
+        jobs = self.expand_chains_device(queries, q_start, q_len, ranked[6], ranked[0], ranked[1], *ranked[2:6], max_chains, keep_secondary, job_capacity)
+        locate = self.locate_window_contigs_device if index.contigs is not None else self.locate_window_device
+        window = locate(index, jobs[4], jobs[5], jobs[6], jobs[7], jobs[8], slack, max_tl)
+        dist_t, dist_q = (max_dist, max_dist) if np.isscalar(max_dist) else max_dist
+        aln = self.align_chain_device(index.ref, window[0], window[1], jobs[9], jobs[3], jobs[4], jobs[5], window[2], jobs[7], jobs[8], max_tl, max_ql,
+                                      dist_t, dist_q, band, zdrop, parameters, **align)
+        described = self.describe_device(index.ref, window[0], window[1], jobs[9], jobs[3], jobs[4], aln[0], aln[4], stride, aln[5], aln[6], md_stride,
+                                         xcigar_stride, binary, xcigar=xcigar)
+        lines = self.classify_alignments_device(jobs[1], jobs[2], aln[0], aln[6], parameters[0], min_score, mask_level)
+        return seeds, chain, ranked, jobs, window, aln, described, lines
+
+    def map_reads_all(self, index, reads, band=64, zdrop=-1, parameters=GATK_PARAMETERS, slack=200, strands=2, max_tl=None, extended=False, **stages):
+        """``map_reads_all_device`` over a list of byte strings.  Returns AllMapResult, per read: ``n_lines`` and ``lines``, a list in
+        line order (the primary first) of Line(ref_beg, ref_end, strand, score, cigar, q_beg, q_end, flag, mapq, parent, nm, n_match,
+        block_len, md, xcigar, rid, rname, status): the alignment spans [ref_beg, ref_end) -- counted from the start of the line's
+        contig where the index has contigs, ``rid`` / ``rname`` set then and None otherwise --, ``cigar``, ``q_beg`` / ``q_end`` are
+        those of the ORIENTED read (what lies outside is a soft clip), ``flag`` has 0x10, 0x100 (secondary) and 0x800
+        (supplementary), ``parent`` is the place in the list of the line this one is secondary to (its own otherwise), ``md`` is
+        bytes and ``xcigar`` the = / X CIGAR with ``extended`` (None otherwise).  An unmapped read has no lines.  ``formats.
+        write_sam_all`` / ``write_paf_all`` take the result as it is."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        n, packed, max_tl, max_ql, stride = _map_setup(reads, dev, slack, max_tl, stages)
+        _, _, _, jobs, window, aln, desc, lines = self.map_reads_all_device(index, *packed, max_tl, max_ql, band, zdrop, parameters, slack=slack, strands=strands,
+                                                                            cigar_stride=stride, xcigar=bool(extended), **stages)
+        torch.cuda.synchronize(dev)
+        job_start, job = jobs[1].cpu().numpy(), jobs[2].cpu().numpy()
+        cap = job.shape[0]
+        t_start, rec, ln, st = window[0].cpu().numpy(), aln[0].cpu().numpy(), aln[5].cpu().numpy(), aln[6].cpu().numpy()
+        cg = aln[4].cpu().numpy().reshape(cap, stride)
+        stats, dst, md = desc[0].cpu().numpy().reshape(cap, 8), desc[3].cpu().numpy(), desc[1].cpu().numpy().reshape(cap, -1)
+        xc = desc[2].cpu().numpy().reshape(cap, -1) if extended else None
+        line, n_lines = lines[0].cpu().numpy(), lines[1].cpu().numpy()
+        contigs = index.contigs
+        rid = window[4].cpu().numpy() if contigs is not None else None
+        out = []
+        for p in range(n):
+            mine = [j for j in range(int(job_start[p]), int(job_start[p + 1])) if line[j, 0] >= 0]
+            mine.sort(key=lambda j: line[j, 0])
+            place = {j: k for k, j in enumerate(mine)}
+            rows = []
+            for j in mine:
+                if dst[j] != 0:  # the alignment stands and its description does not: a text beyond its stride
+                    raise _lib.MglSwError(int(dst[j]), f"describing read {p}")
+                r = int(rid[j]) if rid is not None else None
+                origin = int(contigs.starts[r]) if r is not None else 0
+                nm = int(stats[j, 1] + stats[j, 2] + stats[j, 3])
+                rows.append(Line(int(t_start[j] + rec[j, 1]) - origin, int(t_start[j] + rec[j, 2]) - origin, int(job[j, 2]), int(rec[j, 0]),
+                                 cg[j, :ln[j]].tobytes().decode(), int(rec[j, 3]), int(rec[j, 4]), int(line[j, 1]), int(line[j, 2]), place[int(line[j, 3])], nm,
+                                 int(stats[j, 0]), int(stats[j, 0]) + nm, md[j, :stats[j, 6]].tobytes(), xc[j, :stats[j, 7]].tobytes().decode() if extended else None,
+                                 r, contigs.names[r] if r is not None else None, int(st[j])))
+            out.append(rows)
+        return AllMapResult(n_lines.astype(np.int32), out)
 
     def map_reads_ranked_device(self, index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters=GATK_PARAMETERS, strands=2, max_cand=4096,
                                 cand_capacity=None, seed_out=None, chain_out=None, max_chains=4, min_score=40, min_cnt=3, mask_level=128, rank_anchors=False,

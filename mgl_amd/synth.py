@@ -195,6 +195,26 @@ def mapping_set(seed, count, length=10000, spacer=3000):
     return b"".join(parts), reads, truth
 
 
+def split_mapping_set(seed, count, length=10000, spacer=3000):
+    """Split reads on ``mapping_set(seed, count, length, spacer)``'s reference: read p is a chimera of two windows, the first half of
+    the read of T_p followed by the second half of the read of T_(p + 1) (T_0 behind the last), both as ``chain_pairs`` made them
+    (forward).  Every third read (p % 3 == 2) has its second part reverse-complemented: an inversion, ONE read with a part on each
+    strand.  -> (ref, reads, truth), truth[p] = the read's two parts, each (the position of the part's window in ref, the window's
+    length, the part's strand, q_beg, q_end): the part is read[q_beg:q_end] and lies inside that window, in its first half (part 0)
+    or its second (part 1)."""
+    ref, _, placed = mapping_set(seed, count, length, spacer)
+    pairs = chain_pairs(seed, count, length)
+    reads, truth = [], []
+    for p in range(count):
+        a, b = pairs[p][1], pairs[(p + 1) % count][1]
+        first, second = a[:len(a) // 2], b[len(b) // 2:]
+        inverted = p % 3 == 2
+        reads.append(first + (revcomp(second) if inverted else second))
+        truth.append([(placed[p][0], placed[p][1], 0, 0, len(first)),
+                      (placed[(p + 1) % count][0], placed[(p + 1) % count][1], 1 if inverted else 0, len(first), len(first) + len(second))])
+    return ref, reads, truth
+
+
 def contig_cuts(count, truth, spacer, contigs):
     """The ``contigs`` - 1 positions at which ``mapping_set``'s reference is cut into contigs, ascending: every one inside a spacer
     between two reads (the outer spacers where there is one read), spread over them in order, evenly spaced inside a spacer.  The
