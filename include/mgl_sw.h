@@ -1149,6 +1149,66 @@ int mgl_sw_describe_alignments_batch_device(mgl_sw_ctx *ctx, void *stream, int64
                                             char *d_xcigar_out, int xcigar_stride, int32_t *d_status_out, int flags);
 
 /*
+ * PILING UP ALIGNMENTS (NOT a reference function; opt-in): behind mgl_sw_describe_alignments_batch_device and
+ * mgl_sw_classify_alignments_batch_device, on the same stream, with no copy and no synchronisation in between.  What a batch of
+ * alignments adds up to per position of the reference: base counts, deleted columns, insertions.  Defined by
+ * tests/pileup_textbook.py; DESIGN.md section 9o.
+ * The first thirteen arguments are exactly what mgl_sw_describe_alignments_batch_device takes, with its validity rules, its
+ * MGL_SW_FLAG_BINARY_CIGAR (the only flag read) and its OVER-READ RULE.  (The present kernel reads no target byte at all.)
+ * Alignment p is COUNTED iff d_status_in is NULL or d_status_in[p] == 0, d_select is NULL or d_select[p] != 0, and the alignment
+ * passes that entry's per-alignment check.  Nothing of an alignment that is not counted is read beyond its status and select words.
+ * An alignment is checked whole before its first add: a refused one adds nothing and gets MGL_SW_ERR_BAD_ARG in d_status_out
+ * (optional); a status going in is passed through; a deselected alignment gets 0.
+ * Positions: the absolute position of a target column is its byte offset in d_targets, d_t_start[p] + t_beg + i.  The region is
+ * [region_beg, region_beg + region_len) in those offsets; columns outside it are skipped, what is inside is still counted.
+ * d_counts: eight planes of region_len uint32 each, plane c at c * region_len (channel-major).  The entry ADDS into it: the caller
+ * zeroes it, and several batches may accumulate into one table.  Counts wrap modulo 2^32.
+ *   planes 0-4: per M column, 1 in the plane of the QUERY byte: A / a 0, C / c 1, G / g 2, T / t 3, every other byte 4;
+ *   plane 5:    per column of a D element, 1;
+ *   planes 6, 7: per I element of length L, 1 in plane 6 and L in plane 7 at position P - 1, P the absolute position of the next
+ *               target-consuming column (the target cursor).  This covers a leading I, a trailing I and an I-only alignment.  A
+ *               P - 1 outside the region, -1 included, is not counted; one in front of the alignment's own t_beg or window IS
+ *               counted when it lies in the region.
+ * MGL_SW_ERR_BAD_ARG before any device work for that entry's own refusals (but there is no d_stats_out and there are no texts),
+ * region_beg < 0, region_len outside 1 .. 2^31 - 1 and a null d_counts; MGL_SW_ERR_DEVICE without a GPU.  n = 0 is MGL_SW_OK.
+ * Device work on `stream`, no synchronisation, no workspace: sw_pileup_kernel, one wave per alignment, every add a relaxed atomic
+ * without return -- integers, so the table is bit-exact whatever the order.  No MGL_SW_KERNEL_* id: the timing record keeps its
+ * fill_kernel.
+ */
+int mgl_sw_pileup_alignments_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets, const int64_t *d_t_start,
+                                          const int32_t *d_t_len, const uint8_t *d_queries, const int64_t *d_q_start, const int32_t *d_q_len,
+                                          const mgl_sw_chain_alignment *d_aln, const char *d_cigar, int cigar_stride, const int32_t *d_cigar_len,
+                                          const int32_t *d_status_in, const int32_t *d_select, int64_t region_beg, int64_t region_len,
+                                          uint32_t *d_counts, int32_t *d_status_out, int flags);
+
+/*
+ * CANDIDATE SITES FROM A PILEUP (NOT a reference function; opt-in): what the eight planes of mgl_sw_pileup_alignments_batch_device
+ * say per position.  Defined by tests/pileup_textbook.py; DESIGN.md section 9o.
+ * Per position i of the region, all arithmetic in 64 bits: depth = the sum of planes 0-5; ref = the channel of
+ * d_targets[region_beg + i]; call = the channel 0-5 with the largest count (5 is the deletion), the lowest channel winning a tie;
+ * alt = the channel 0-4 other than ref with the largest count, the lowest winning a tie, -1 where that count is 0.
+ * flags: 1 (covered) depth >= min_depth; with ok(x) := x >= min_alt and x * 256 >= min_frac * depth: 2 (SNV candidate) covered and
+ * ok(alt_count); 4 (deletion) covered and ok(plane 5); 8 (insertion behind this position) covered and ok(plane 6).
+ * d_call_out[i] (optional) = "ACGTN*"[call], N where the position is not covered; d_flags_out[i] (optional) = the flags.
+ * A SITE is a position with flags & 14.  The sites are written in position order into d_sites_out (mgl_sw_site; pos counts from
+ * region_beg; depth, call_count and alt_count clipped to 2^31 - 1), only the first site_capacity of them; d_n_sites_out[0] is the
+ * total, those beyond the capacity included, so site_capacity = 0 (d_sites_out may be NULL then) is a sizing pass.
+ * MGL_SW_ERR_BAD_ARG before any device work for a null d_counts, d_targets or d_n_sites_out, a null d_sites_out with
+ * site_capacity > 0, region_len outside 1 .. 2^31 - 1, region_beg < 0, min_depth < 1, min_alt < 1, min_frac outside 1 .. 256 and
+ * site_capacity outside 0 .. 2^30; MGL_SW_ERR_DEVICE without a GPU; MGL_SW_ERR_NOMEM where the workspace limit does not hold 16 bytes
+ * per 256 positions and the scan's storage.
+ * Device work on `stream`, no synchronisation, one workspace: sw_pileup_flag_kernel (a thread per position), a device-wide scan of
+ * the blocks' site counts, sw_pileup_write_kernel.  No MGL_SW_KERNEL_* id: the timing record keeps its fill_kernel.
+ */
+typedef struct mgl_sw_site {
+    int32_t pos, flags, depth, ref, call, call_count, alt, alt_count;
+} mgl_sw_site;
+
+int mgl_sw_pileup_sites_device(mgl_sw_ctx *ctx, void *stream, const uint32_t *d_counts, int64_t region_len, const uint8_t *d_targets,
+                               int64_t region_beg, int min_depth, int min_alt, int min_frac, uint8_t *d_call_out, uint8_t *d_flags_out,
+                               mgl_sw_site *d_sites_out, int64_t site_capacity, int64_t *d_n_sites_out);
+
+/*
  * Logical backtrack matrix of one pair, the reference's calculateMatrix
  * (sw_scalar.h:7 / sw.cpp:5-146): btr is (tl+1)*(ql+1) int32 row-major with
  * row 0 / column 0 zero, +k = k rows up (deletion run), -k = k columns left

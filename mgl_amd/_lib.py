@@ -40,6 +40,7 @@ SYMBOLS = (
     "mgl_sw_rank_chains_batch_device", "mgl_sw_describe_alignments_batch_device", "mgl_sw_index_build_contigs_device",
     "mgl_sw_index_get_contigs", "mgl_sw_index_contig_of_batch_device", "mgl_sw_chain_anchors_grouped_batch_device",
     "mgl_sw_locate_window_contigs_batch_device", "mgl_sw_expand_chains_batch_device", "mgl_sw_classify_alignments_batch_device",
+    "mgl_sw_pileup_alignments_batch_device", "mgl_sw_pileup_sites_device",
 )
 # MGL_SW_VERSION of the include/mgl_sw.h this mirror was written against: the structs below (Plan, Timing) are that header's, and the
 # library writes sizeof(ITS struct) through the pointers it is given -- so a library of another version is refused at load time
@@ -94,6 +95,11 @@ class Line(C.Structure):
 class AlignmentStats(C.Structure):
     """mgl_sw_alignment_stats: what one alignment's CIGAR says about its spans (mgl_sw_describe_alignments_batch_device)."""
     _fields_ = [(n, C.c_int32) for n in ("n_match", "n_mismatch", "n_ins", "n_del", "n_ins_runs", "n_del_runs", "md_len", "xcigar_len")]
+
+
+class Site(C.Structure):
+    """mgl_sw_site: one candidate site of a pileup (mgl_sw_pileup_sites_device)."""
+    _fields_ = [(n, C.c_int32) for n in ("pos", "flags", "depth", "ref", "call", "call_count", "alt", "alt_count")]
 
 
 class Timing(C.Structure):
@@ -235,6 +241,9 @@ def lib():
     L.mgl_sw_expand_chains_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int,
                                                     C.c_int64] + [vp] * 11
     L.mgl_sw_classify_alignments_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int, C.c_int] + [vp] * 4
+    L.mgl_sw_pileup_alignments_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int64, C.c_int64, vp, vp,
+                                                        C.c_int]
+    L.mgl_sw_pileup_sites_device.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int64, vp]
     L.mgl_sw_backtrack_matrix.argtypes = [cp, C.c_int, cp, C.c_int] + [C.c_int] * 5 + [i32p, C.POINTER(Score)]
     L.mgl_sw_cigar_from_backtrack.argtypes = [i32p, C.c_int, C.c_int, C.c_int, C.POINTER(Score), cp, C.c_int,
                                               C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -426,3 +426,28 @@ def read_sam(path):
                                      [] if c[5] == "*" else cigar_text_to_elements(c[5]), b"" if c[9] == "*" else c[9].encode(),
                                      b"" if c[10] == "*" else bytes(ord(x) - 33 for x in c[10]), tags))
     return "\n".join(header) + ("\n" if header else ""), refs, records
+
+
+def write_sites(path, ref_name, ref_len, sites, counts, starts=None):
+    """One tab-separated line per candidate site of a pileup (MicrosoftSmithWaterman.pileup_sites_device, read back): contig, 1-based
+    position, reference base, call, depth, the eight counts of the position (A C G T other, deleted, insertions, inserted bases) and
+    the flags (1 covered, 2 SNV candidate, 4 deletion, 8 insertion behind the position).  ``sites``: rows of mgl_sw_site's eight
+    fields, pos counted from the table's first position; ``counts``: the table [8, region_len].  ``ref_name`` and ``ref_len`` as
+    ``write_sam`` takes them; as lists (one entry per contig) they want ``starts``, the contigs' first positions in the table, and a
+    site's position counts from the start of its contig.  A list of candidates, no VCF: no genotype and no quality is claimed."""
+    names, lens, many = _targets(ref_name, ref_len)
+    if many and (starts is None or len(starts) != len(names)):
+        raise ValueError("a reference of contigs wants starts: the first position of every contig")
+    first = np.asarray(starts if many else [0], np.int64)
+    counts = np.asarray(counts).reshape(8, -1)
+    if counts.dtype == np.int32:  # (the device form's tensor carries the uint32 bits)
+        counts = counts.view(np.uint32)
+    with open(path, "wt") as f:
+        f.write("#contig\tpos\tref\tcall\tdepth\tA\tC\tG\tT\tother\tdel\tins\tins_bases\tflags\n")
+        for row in np.asarray(sites).reshape(-1, 8):
+            pos, flags, depth, ref, call = (int(v) for v in row[:5])
+            c = int(np.searchsorted(first, pos, side="right")) - 1
+            if c < 0 or pos - int(first[c]) >= lens[c]:
+                raise ValueError("site at %d lies in no contig" % pos)
+            f.write("\t".join([names[c], str(pos - int(first[c]) + 1), "ACGTN"[ref], "ACGTN*"[call], str(depth)] + [str(int(v)) for v in counts[:, pos]] +
+                              [str(flags)]) + "\n")

@@ -1158,6 +1158,11 @@ class MicrosoftSmithWaterman:
         _, _, _, jobs, window, aln, desc, lines = self.map_reads_all_device(index, *packed, max_tl, max_ql, band, zdrop, parameters, slack=slack, strands=strands,
                                                                             cigar_stride=stride, xcigar=bool(extended), **stages)
         torch.cuda.synchronize(dev)
+        return self._all_result(index, n, stride, jobs, window, aln, desc, lines, extended)
+
+    @staticmethod
+    def _all_result(index, n, stride, jobs, window, aln, desc, lines, extended):
+        """The device tuples of ``map_reads_all_device``, read back (the stream is done) -> AllMapResult."""
         job_start, job = jobs[1].cpu().numpy(), jobs[2].cpu().numpy()
         cap = job.shape[0]
         t_start, rec, ln, st = window[0].cpu().numpy(), aln[0].cpu().numpy(), aln[5].cpu().numpy(), aln[6].cpu().numpy()
@@ -1345,6 +1350,124 @@ class MicrosoftSmithWaterman:
         return (ContigDescribedMapResult if contig else DescribedMapResult)(
             *fields, mapq, nc, secondary, z(rec[:, 3]), z(rec[:, 4]), nm, stats[:, 0].astype(np.int32), (stats[:, 0] + nm).astype(np.int32), mds,
             CigarColumn(desc[2].cpu().numpy().reshape(n, -1), stats[:, 7].astype(np.int32)) if extended else None, *contig)
+
+    def pileup_device(self, targets, t_start, t_len, queries, q_start, q_len, aln, cigar, cigar_stride, cigar_len, status_in=None, select=None,
+                      region=None, counts=None, binary_cigar=False, out=None):
+        """mgl_sw_pileup_alignments_batch_device on device tensors: ``describe_device``'s first eleven arguments, optionally a
+        ``select`` [n] int32 (an alignment with a zero is not counted) and ``region`` = (beg, len) in byte offsets of ``targets``, by
+        default the whole of it (tests/pileup_textbook.py); enqueued on the current stream, not synchronised.  Returns (counts
+        [8, region_len] int32 -- the uint32 bits; planes A C G T other, deleted, insertions, inserted bases --, status [n]).  The entry
+        ADDS: ``counts=None`` allocates zeros, a tensor given accumulates.  ``out``: a (counts, status) tuple to write into (its
+        status may be None)."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(t_start.numel())
+        dev = targets.device
+        beg, length = (0, int(targets.numel())) if region is None else (int(region[0]), int(region[1]))
+        if out is None:
+            out = (torch.zeros((8, max(length, 0)), dtype=torch.int32, device=dev) if counts is None else counts, _alloc(dev)(n))
+        table, st = out
+        assert table.numel() >= 8 * length and table.dtype == torch.int32 and table.is_contiguous() and (st is None or st.numel() >= n)
+        ptr = _ptrs(dev)
+        rc = _lib.lib().mgl_sw_pileup_alignments_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len), ptr(aln),
+            ptr(cigar), int(cigar_stride), ptr(cigar_len), ptr(status_in), ptr(select), beg, length, ptr(table), ptr(st),
+            _lib.FLAG_BINARY_CIGAR if binary_cigar else 0)
+        _check(rc, ctx)
+        return out
+
+    def pileup_sites_device(self, counts, ref, region_beg=0, min_depth=4, min_alt=2, min_frac=64, site_capacity=None, call=True, flags=True, out=None):
+        """mgl_sw_pileup_sites_device on device tensors: ``pileup_device``'s counts [8, region_len] and the reference bytes they were
+        piled up over (position i of the table is ``ref[region_beg + i]``); enqueued on the current stream, not synchronised.  Returns
+        (call [region_len] uint8 or None, flags [region_len] uint8 or None, sites [site_capacity, 8] int32 -- mgl_sw_site's fields,
+        in position order --, n_sites [1] int64: the total, those beyond the capacity included).  ``site_capacity`` defaults to
+        region_len; 0 is a sizing pass.  ``out``: such a tuple to write into, whose tensors decide what is written."""
+        import torch
+
+        ctx = self._ensure()
+        dev = counts.device
+        length = int(counts.numel()) // 8
+        if out is None:
+            cap = length if site_capacity is None else int(site_capacity)
+            new = _alloc(dev)
+            out = (new(length, torch.uint8) if call else None, new(length, torch.uint8) if flags else None, new((max(cap, 0), 8)), new(1, torch.int64))
+        cl, fl, sites, ns = out
+        cap = (int(sites.numel()) // 8 if sites is not None else 0) if site_capacity is None else int(site_capacity)
+        assert counts.is_contiguous() and (sites is None or sites.numel() >= 8 * cap) and all(x is None or x.numel() >= length for x in (cl, fl))
+        assert ref.numel() >= int(region_beg) + length
+        ptr = _ptrs(dev)
+        rc = _lib.lib().mgl_sw_pileup_sites_device(ctx, torch.cuda.current_stream(dev).cuda_stream, ptr(counts), length, ptr(ref), int(region_beg),
+                                                   int(min_depth), int(min_alt), int(min_frac), ptr(cl), ptr(fl), ptr(sites), cap, ptr(ns))
+        _check(rc, ctx)
+        return out
+
+    def pileup(self, refs, alts, cigars, spans=None, positions=None, region=None, binary_cigar=False, return_status=False):
+        """mgl_sw_pileup_alignments_batch_device over lists: ``describe``'s alignments, ``positions[k]`` the absolute position of
+        ``refs[k][0]`` (by default the targets lie end to end), ``region`` = (beg, len), by default from 0 to the end of the last
+        target.  NOT a reference function.  Returns counts, a numpy uint32 array [8, region_len]; with ``return_status`` also the
+        status array, and no exception for an alignment's status."""
+        import torch
+
+        from . import formats
+
+        dev = torch.device("cuda", self._device)
+        n, packed, _ = _pack_pairs(refs, alts, dev, 16, False)
+        assert len(cigars) == n
+        if binary_cigar:
+            rows = [formats.cigar_elements_to_binary(formats.cigar_text_to_elements(c)).astype("<u4").tobytes() for c in cigars]
+        else:
+            rows = [c.encode() if isinstance(c, str) else bytes(c) for c in cigars]
+        stride = (max([len(r) for r in rows] + [4]) + 3) // 4 * 4
+        slots = np.zeros((n, stride), np.uint8)
+        for k, r in enumerate(rows):
+            slots[k, :len(r)] = np.frombuffer(r, np.uint8)
+        if spans is None:
+            spans = [(0, len(t), 0, len(q)) for t, q in zip(refs, alts)]
+        rec = np.zeros((n, 8), np.int32)
+        rec[:, 1:5] = np.asarray(spans, np.int32).reshape(n, 4)
+        g = lambda x: _upload(x, dev)  # noqa: E731
+        t_start = packed[1] if positions is None else g(np.asarray(positions, np.int64))
+        if region is None:
+            ends = [int(p) + len(t) for p, t in zip(t_start.cpu().numpy(), refs)]
+            region = (0, max(ends + [1]))
+        got = self.pileup_device(packed[0], t_start, packed[2], *packed[3:6], g(rec), g(slots.reshape(-1)), stride,
+                                 g(np.asarray([len(r) for r in rows], np.int32)), region=region, binary_cigar=binary_cigar)
+        counts, st = _fetch(got, dev, return_status)
+        counts = counts.view(np.uint32)
+        return (counts, st) if return_status else counts
+
+    def map_reads_pileup_device(self, index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters=GATK_PARAMETERS, counts=None, min_mapq=0,
+                                **stages):
+        """``map_reads_all_device`` and ``pileup_device`` behind it over [0, ref_len), on the current stream, nothing read back and
+        nothing synchronised in between.  The pileup takes exactly the tensors ``map_reads_all_device`` hands ``describe_device``, the
+        alignment status, and a select made on the device from the lines: a job is counted where it is a line (order >= 0), not a
+        secondary one (flag & 0x100 == 0) and its mapq is at least ``min_mapq``.  (The line rows of the empty jobs are uninitialised;
+        their alignment status is non-zero, and the status is what excludes them.)  ``counts``: a table to add into, so that batches
+        accumulate.  ``stages``: the further arguments of ``map_reads_all_device``.  Returns its eight tuples and (counts, status)."""
+        binary = bool(stages.get("binary_cigar", False))
+        if stages.get("cigar_stride") is None:
+            stages["cigar_stride"] = _default_stride(max_tl, max_ql, binary)
+        stride = int(stages["cigar_stride"])
+        res = self.map_reads_all_device(index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters, **stages)
+        jobs, window, aln, lines = res[3], res[4], res[5], res[7][0]
+        select = ((lines[:, 0] >= 0) & ((lines[:, 1] & 0x100) == 0) & (lines[:, 2] >= int(min_mapq))).to(lines.dtype)
+        piled = self.pileup_device(index.ref, window[0], window[1], jobs[9], jobs[3], jobs[4], aln[0], aln[4], stride, aln[5], aln[6], select,
+                                   (0, int(index.info.ref_len)), counts, binary)
+        return res + (piled,)
+
+    def map_reads_pileup(self, index, reads, band=64, zdrop=-1, parameters=GATK_PARAMETERS, slack=200, strands=2, max_tl=None, counts=None, min_mapq=0,
+                         **stages):
+        """``map_reads_pileup_device`` over a list of byte strings.  Returns (AllMapResult as ``map_reads_all`` gives it, counts: a
+        numpy uint32 array [8, ref_len]).  ``counts``: a device table of an earlier batch to add into."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        n, packed, max_tl, max_ql, stride = _map_setup(reads, dev, slack, max_tl, stages)
+        res = self.map_reads_pileup_device(index, *packed, max_tl, max_ql, band, zdrop, parameters, counts=counts, min_mapq=min_mapq, slack=slack,
+                                           strands=strands, cigar_stride=stride, xcigar=False, **stages)
+        torch.cuda.synchronize(dev)
+        return self._all_result(index, n, stride, *res[3:8], False), res[8][0].cpu().numpy().view(np.uint32)
 
     def align_packed_2bit(self, target_bases, target_base_count, t_start, t_len, query_bases, query_base_count, q_start, q_len,
                           max_tl, max_ql, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,

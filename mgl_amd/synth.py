@@ -261,3 +261,45 @@ def repeat_mapping_set(seed, count, length=10000, spacer=3000, copies=0, diverge
         parts.append(BASES[rng.integers(4, size=spacer)].tobytes())
         at += n + spacer
     return b"".join(parts), reads, truth, copy
+
+
+def variant_mapping_set(seed, ref_len=8000, read_len=1000, step=125, snvs=10, dele=3, ins=2):
+    """A random reference, a DONOR copy of it with ``snvs`` substitutions, one deletion of ``dele`` bases and one insertion of ``ins``
+    bases, and reads that tile the donor exactly: one of ``read_len`` every ``step`` bases, every odd one reverse-complemented.  The
+    variants lie at least 300 bases apart and 1 000 from either end; the bases of an indel differ from both bases next to it (the
+    reference is changed there to make it so), so the indel has one placement.
+    -> (ref, reads, planted), planted a list in position order of ("X", pos, the donor's base), ("D", pos of the first deleted base,
+    the deleted bases) and ("I", the position the insertion stands behind, the inserted bases), positions those of the reference."""
+    rng = np.random.default_rng([seed, ref_len, read_len, step, snvs, dele, ins])
+    count, apart, edge = snvs + 2, 300, 1000
+    free = ref_len - 2 * edge - (count - 1) * apart - dele - 2
+    assert free >= 0, "the reference does not hold the variants 300 apart and 1 000 from its ends"
+    at = edge + np.sort(rng.integers(0, free + 1, count)) + apart * np.arange(count)
+    kinds = ["X"] * count
+    d, i = (int(x) for x in rng.choice(count, 2, replace=False))
+    kinds[d], kinds[i] = "D", "I"
+    ref = bytearray(random_genome(rng, ref_len).tobytes())
+    pick = lambda avoid: int(rng.choice([b for b in b"ACGT" if b not in avoid]))  # noqa: E731
+    planted = []
+    for kind, pos in zip(kinds, (int(x) for x in at)):
+        if kind == "X":
+            planted.append(("X", pos, bytes([pick((ref[pos],))])))
+        elif kind == "D":
+            for k in range(pos, pos + dele):
+                ref[k] = pick((ref[pos - 1], ref[pos + dele]))
+            planted.append(("D", pos, bytes(ref[pos:pos + dele])))
+        else:
+            planted.append(("I", pos, bytes(pick((ref[pos], ref[pos + 1])) for _ in range(ins))))
+    donor, shift = bytearray(ref), 0
+    for kind, pos, what in planted:
+        if kind == "X":
+            donor[pos + shift] = what[0]
+        elif kind == "D":
+            del donor[pos + shift:pos + shift + dele]
+            shift -= dele
+        else:
+            donor[pos + shift + 1:pos + shift + 1] = what
+            shift += ins
+    donor = bytes(donor)
+    reads = [donor[s:s + read_len] for s in range(0, len(donor) - read_len + 1, step)]
+    return bytes(ref), [revcomp(r) if k % 2 else r for k, r in enumerate(reads)], planted
