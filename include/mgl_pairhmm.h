@@ -74,7 +74,8 @@ int mgl_pairhmm_compute_pairs(mgl_pairhmm_ctx *ctx, int64_t n_pairs, int64_t n_r
 
 /* The same with every pointer in device memory, enqueued on `stream` (a hipStream_t; NULL = the context's
  * own stream); nothing is copied or synchronised.  max_read_len / max_hap_len bound the lengths in the batch.
- * d_used_double (optional, int32 per pair) reports which pairs were rescued in double. */
+ * d_used_double (optional, int32 per pair) reports which pairs were rescued in double: 1 or 0 for every pair of a float
+ * batch.  In double mode (mgl_pairhmm_initialize with use_double) nothing is rescued and the array is not written. */
 int mgl_pairhmm_compute_pairs_device(mgl_pairhmm_ctx *ctx, void *stream, int64_t n_pairs, const uint8_t *d_reads_data,
                                      const int64_t *d_read_off, const uint8_t *d_haps_data, const int64_t *d_hap_off,
                                      const int32_t *d_pair_read, const int32_t *d_pair_hap, int max_read_len, int max_hap_len,
