@@ -3,6 +3,7 @@ and the streams for every BASELINE.json config and for each kernel's crossover, 
 not as a silent change of a bench line."""
 import pytest
 
+import strip_cases
 from mgl_amd import _lib
 
 GATK = (200, -150, 260, 11)
@@ -87,7 +88,9 @@ def test_configs0_plumbing_case_is_the_int32_kernel():
 
 def test_configs3_long_reads_take_the_strip_kernel():
     p = plan(n=2304, max_tl=10300, max_ql=10300, parameters=GATK, workspace=BENCH_WS)
-    assert p.fill_kernel == STRIP16 and p.waves_per_pair == 4 and 20 <= p.rows <= 32 and p.precision_bits == 16
+    lo, hi = strip_cases.height_interval(21, 4)   # 10 241 .. 10 752 rows on the 512 strip slots of four waves: 21 rows a strip
+    assert lo <= 10300 <= hi
+    assert p.fill_kernel == STRIP16 and p.waves_per_pair == 4 and p.rows == 21 and p.precision_bits == 16
     assert p.chunk_pairs == 2304 and p.chunks == 1, "17 MB of kept rows per pair: the whole batch is one launch (three chunks measured slower)"
     p = plan(n=2304, max_tl=10300, max_ql=10300, parameters=GATK, workspace=16 << 30)
     assert p.fill_kernel == STRIP16 and p.chunks > 1 and p.workspace_halves == 2, "a smaller workspace: chunks, two halves in flight"
