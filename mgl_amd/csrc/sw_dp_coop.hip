@@ -881,9 +881,6 @@ int coop_lds_bytes(int sps_cap, int waves_per_block)
     return coop_query_bytes(sps_cap) + waves_per_block * (RING_COLS * 8 + 8 + 8) + 32;
 }
 
-// Is the 16-bit form worth trying for these (normalised) parameters?  The 64 PEs of a half-stripe span about
-// 64 * (match + 2e) (+ 2(o - e)); with the window check's margins that must stay inside 16 bits, else every pair would only
-// fall back.  (Exactness never depends on this estimate: the kernel checks the real window.)
 int coop16_lds_bytes(int sps_cap, int waves_per_block) { return coop_lds_bytes(sps_cap, waves_per_block) + coop_query_bytes(sps_cap); } // two query copies
 
 // Can the kernel run at all: its packed constants and the margins of the window check must fit 16 bits
@@ -892,6 +889,9 @@ bool coop16_possible(int match, int mismatch, int gopen, int gext)
     if (match <= 0 || mismatch > match || gext < 0 || gopen < gext || match > 4000 || mismatch < -4000 || gopen > 4000 || gext > 4000) return false;
     return coop16_below(match, mismatch, gopen, gext) + coop16_above(match, gopen, gext) <= 60000;
 }
+// Is the 16-bit form worth trying for these (normalised) parameters?  The 128 PEs of a double stripe span about
+// 128 * (match + 2e) (+ 2(o - e)); with the window check's margins that must stay inside 16 bits, else every pair would only
+// fall back.  (Exactness never depends on this estimate: the kernel checks the real window.)
 bool coop16_worthwhile(int match, int mismatch, int gopen, int gext)
 {
     if (!coop16_possible(match, mismatch, gopen, gext)) return false;
