@@ -1209,6 +1209,80 @@ int mgl_sw_pileup_sites_device(mgl_sw_ctx *ctx, void *stream, const uint32_t *d_
                                mgl_sw_site *d_sites_out, int64_t site_capacity, int64_t *d_n_sites_out);
 
 /*
+ * THE INSERTIONS AT THE SITES (NOT a reference function; opt-in): behind mgl_sw_pileup_sites_device, on the same stream, over the
+ * alignments the pileup took.  Which lengths and which bases the insertions behind the candidate sites have.  Defined by
+ * tests/calls_textbook.py; DESIGN.md section 9p.
+ * The first fifteen arguments are exactly what mgl_sw_pileup_alignments_batch_device takes, with its validity rules, its COUNTED
+ * rule, its per-alignment check before the first add, its status passing, its MGL_SW_FLAG_BINARY_CIGAR (the only flag read) and its
+ * OVER-READ RULE.  region_beg is that entry's: a site's pos counts from it.
+ * THE ACTIVE SITES are the first S = min(max(d_n_sites[0], 0), site_capacity) records of d_sites, read on the device: nothing is read
+ * back.  Their pos is taken as strictly ascending, as mgl_sw_pileup_sites_device writes it; the lookup stays inside those S records
+ * whatever they hold -- an unsorted list gives unspecified counts, never an access outside the arrays.
+ * d_ins: site_capacity rows of W = 6 * max_ins + 1 uint32.  The entry ADDS into it: the caller zeroes it, and several batches may
+ * accumulate over one site list.  Counts wrap modulo 2^32.  In row s:
+ *   word 0:                        the insertions longer than max_ins;
+ *   word L (1 <= L <= max_ins):    the insertions of exactly L bases;
+ *   word max_ins + 1 + 5 * j + ch: channel ch (A / a 0, C / c 1, G / g 2, T / t 3, every other byte 4) in column j of the insertions
+ *                                  of at most max_ins bases.
+ * An I element of length L of a counted alignment stands behind absolute position P - 1 (the pileup's rule) and matches site s iff
+ * sites[s].pos == P - 1 - region_beg among the active sites, whatever flags the site has.  A match with L > max_ins adds 1 to word 0;
+ * any other match adds 1 to word L and, per inserted base j < L, 1 to its column's channel word; no match adds nothing.
+ * MGL_SW_ERR_BAD_ARG before any device work for the pileup entry's own refusals (there is no region_len and no d_counts), max_ins
+ * outside 1 .. 64, a null d_sites, d_n_sites or d_ins and site_capacity outside 1 .. 2^30; MGL_SW_ERR_DEVICE without a GPU.  n = 0
+ * is MGL_SW_OK.
+ * Device work on `stream`, no synchronisation, no workspace: sw_insertions_kernel, one wave per alignment, every add a relaxed atomic
+ * without return.  No MGL_SW_KERNEL_* id: the timing record keeps its fill_kernel.
+ */
+int mgl_sw_pileup_insertions_batch_device(mgl_sw_ctx *ctx, void *stream, int64_t n, const uint8_t *d_targets, const int64_t *d_t_start,
+                                          const int32_t *d_t_len, const uint8_t *d_queries, const int64_t *d_q_start, const int32_t *d_q_len,
+                                          const mgl_sw_chain_alignment *d_aln, const char *d_cigar, int cigar_stride, const int32_t *d_cigar_len,
+                                          const int32_t *d_status_in, const int32_t *d_select, int64_t region_beg, const mgl_sw_site *d_sites,
+                                          const int64_t *d_n_sites, int64_t site_capacity, int max_ins, uint32_t *d_ins, int32_t *d_status_out,
+                                          int flags);
+
+/*
+ * EVENTS, GENOTYPES AND QUALITIES OF THE SITES (NOT a reference function; opt-in): what the planes of
+ * mgl_sw_pileup_alignments_batch_device, the sites of mgl_sw_pileup_sites_device and the rows of
+ * mgl_sw_pileup_insertions_batch_device (d_ins; NULL: no insertion is called) say per site.  Integers only.  Defined by
+ * tests/calls_textbook.py; DESIGN.md section 9p.
+ * The active sites are that entry's.  A site whose pos lies outside 0 .. region_len - 1 has no event.  With c[k] the planes at the
+ * site's position read unclipped, depth = c[0] + .. + c[5] and ref the channel of d_targets[region_beg + pos], the EVENTS of active
+ * site s, in this order:
+ *   SNV (kind 1):       flags & 2, ref <= 3 and the site's alt in 0 .. 3.  r = c[ref], a = c[alt], len = 1.
+ *   deletion (kind 2):  flags & 4, and site s - 1 is not a deletion site (flags & 4) at pos - 1: the first position of a run.  len =
+ *                       the number of consecutive active sites from s with consecutive pos and flags & 4, counted up to max_del; call
+ *                       flag 1 where the run goes on beyond max_del (the rest of the run gives no call).  r = c[ref] (plane 4 for
+ *                       a reference byte outside ACGT), a = c[5], alt = -1.
+ *   insertion (kind 3): flags & 8, d_ins given and some word 1 .. max_ins of row s non-zero.  len = the L with the largest word,
+ *                       the smallest on a tie; a = that word, r = max(depth - c[6], 0), alt = -1.
+ * THE GENOTYPE, in 64 bits: L0 = r * cost_match + a * cost_error, L1 = (r + a) * cost_het, L2 = a * cost_match + r * cost_error,
+ * m = their minimum, PLg = min((Lg - m + 128) >> 8, 2^31 - 1); gt = the lowest g with Lg == m (0 = 0/0, 1 = 0/1, 2 = 1/1);
+ * gq = min(99, the smaller PL of the other two); qual = PL0.  The costs are in 1/256 phred per read.  Every event is written, a 0/0
+ * one included.
+ * The calls are written in site order, inside a site SNV, deletion, insertion, into d_calls_out, only the first call_capacity of
+ * them; d_n_calls_out[0] is the total, those beyond the capacity included, so call_capacity = 0 (d_calls_out may be NULL then) is a
+ * sizing pass.  depth, ref_count and alt_count are clipped to 2^31 - 1 on the way out only.  d_ins_seq_out (required when d_ins is
+ * given and call_capacity > 0, optional otherwise): call_capacity rows of max_ins bytes; the row of a written insertion call gets,
+ * per column j < len, "ACGTN"[ch] of the channel with the largest count (the lowest on a tie) and 0 behind; the row of a written call
+ * of another kind gets zeros.
+ * MGL_SW_ERR_BAD_ARG before any device work for a null d_counts, d_targets, d_sites, d_n_sites or d_n_calls_out, region_len outside
+ * 1 .. 2^31 - 1, region_beg < 0, site_capacity outside 1 .. 2^30, max_ins outside 1 .. 64, max_del outside 1 .. 4096, a cost outside
+ * 1 .. 2^20 or not cost_match < cost_het < cost_error, call_capacity outside 0 .. 2^30, a null d_calls_out with call_capacity > 0
+ * and a null d_ins_seq_out with d_ins and call_capacity > 0; MGL_SW_ERR_DEVICE without a GPU; MGL_SW_ERR_NOMEM where the workspace
+ * limit does not hold 16 bytes per 256 site slots and the scan's storage.
+ * Device work on `stream`, no synchronisation, one workspace: sw_genotype_count_kernel (a thread per site slot), a device-wide scan
+ * of the blocks' event counts, sw_genotype_write_kernel.  No MGL_SW_KERNEL_* id: the timing record keeps its fill_kernel.
+ */
+typedef struct mgl_sw_call {
+    int32_t pos, kind, len, ref, alt, depth, ref_count, alt_count, gt, gq, qual, pl0, pl1, pl2, flags, reserved;
+} mgl_sw_call;
+
+int mgl_sw_genotype_sites_device(mgl_sw_ctx *ctx, void *stream, const uint32_t *d_counts, int64_t region_len, const uint8_t *d_targets,
+                                 int64_t region_beg, const mgl_sw_site *d_sites, const int64_t *d_n_sites, int64_t site_capacity,
+                                 const uint32_t *d_ins, int max_ins, int max_del, int cost_match, int cost_het, int cost_error,
+                                 mgl_sw_call *d_calls_out, int64_t call_capacity, int64_t *d_n_calls_out, uint8_t *d_ins_seq_out);
+
+/*
  * Logical backtrack matrix of one pair, the reference's calculateMatrix
  * (sw_scalar.h:7 / sw.cpp:5-146): btr is (tl+1)*(ql+1) int32 row-major with
  * row 0 / column 0 zero, +k = k rows up (deletion run), -k = k columns left

@@ -40,7 +40,8 @@ SYMBOLS = (
     "mgl_sw_rank_chains_batch_device", "mgl_sw_describe_alignments_batch_device", "mgl_sw_index_build_contigs_device",
     "mgl_sw_index_get_contigs", "mgl_sw_index_contig_of_batch_device", "mgl_sw_chain_anchors_grouped_batch_device",
     "mgl_sw_locate_window_contigs_batch_device", "mgl_sw_expand_chains_batch_device", "mgl_sw_classify_alignments_batch_device",
-    "mgl_sw_pileup_alignments_batch_device", "mgl_sw_pileup_sites_device",
+    "mgl_sw_pileup_alignments_batch_device", "mgl_sw_pileup_sites_device", "mgl_sw_pileup_insertions_batch_device",
+    "mgl_sw_genotype_sites_device",
 )
 # MGL_SW_VERSION of the include/mgl_sw.h this mirror was written against: the structs below (Plan, Timing) are that header's, and the
 # library writes sizeof(ITS struct) through the pointers it is given -- so a library of another version is refused at load time
@@ -100,6 +101,12 @@ class AlignmentStats(C.Structure):
 class Site(C.Structure):
     """mgl_sw_site: one candidate site of a pileup (mgl_sw_pileup_sites_device)."""
     _fields_ = [(n, C.c_int32) for n in ("pos", "flags", "depth", "ref", "call", "call_count", "alt", "alt_count")]
+
+
+class Call(C.Structure):
+    """mgl_sw_call: one event of a candidate site with its genotype (mgl_sw_genotype_sites_device)."""
+    _fields_ = [(n, C.c_int32) for n in ("pos", "kind", "len", "ref", "alt", "depth", "ref_count", "alt_count", "gt", "gq", "qual", "pl0", "pl1", "pl2",
+                                         "flags", "reserved")]
 
 
 class Timing(C.Structure):
@@ -244,6 +251,9 @@ def lib():
     L.mgl_sw_pileup_alignments_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int64, C.c_int64, vp, vp,
                                                         C.c_int]
     L.mgl_sw_pileup_sites_device.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int64, vp]
+    L.mgl_sw_pileup_insertions_batch_device.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int64, vp, vp, C.c_int64,
+                                                        C.c_int, vp, vp, C.c_int]
+    L.mgl_sw_genotype_sites_device.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp] + [C.c_int] * 5 + [vp, C.c_int64, vp, vp]
     L.mgl_sw_backtrack_matrix.argtypes = [cp, C.c_int, cp, C.c_int] + [C.c_int] * 5 + [i32p, C.POINTER(Score)]
     L.mgl_sw_cigar_from_backtrack.argtypes = [i32p, C.c_int, C.c_int, C.c_int, C.POINTER(Score), cp, C.c_int,
                                               C.POINTER(C.c_int), C.POINTER(C.c_int)]

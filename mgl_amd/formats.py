@@ -434,7 +434,8 @@ def write_sites(path, ref_name, ref_len, sites, counts, starts=None):
     the flags (1 covered, 2 SNV candidate, 4 deletion, 8 insertion behind the position).  ``sites``: rows of mgl_sw_site's eight
     fields, pos counted from the table's first position; ``counts``: the table [8, region_len].  ``ref_name`` and ``ref_len`` as
     ``write_sam`` takes them; as lists (one entry per contig) they want ``starts``, the contigs' first positions in the table, and a
-    site's position counts from the start of its contig.  A list of candidates, no VCF: no genotype and no quality is claimed."""
+    site's position counts from the start of its contig.  A list of candidates, no VCF: no genotype and no quality is claimed
+    (``write_vcf`` writes the calls of ``map_reads_calls``)."""
     names, lens, many = _targets(ref_name, ref_len)
     if many and (starts is None or len(starts) != len(names)):
         raise ValueError("a reference of contigs wants starts: the first position of every contig")
@@ -451,3 +452,87 @@ def write_sites(path, ref_name, ref_len, sites, counts, starts=None):
                 raise ValueError("site at %d lies in no contig" % pos)
             f.write("\t".join([names[c], str(pos - int(first[c]) + 1), "ACGTN"[ref], "ACGTN*"[call], str(depth)] + [str(int(v)) for v in counts[:, pos]] +
                               [str(flags)]) + "\n")
+
+
+# --------------------------------------------------------------------------------------------- VCF
+VcfRecord = namedtuple("VcfRecord", "chrom pos ref alt qual filter gt gq dp ad pl")
+VcfRecord.__doc__ = "one line of read_vcf: pos counts from 0; ref and alt are bytes; gt is the text (0/1, 1/1); ad and pl are tuples"
+
+
+def write_vcf(path, ref_name, ref_len, ref, calls, starts=None, min_qual=0, sample="sample"):
+    """A VCFv4.2 file of one sample from the calls of ``MicrosoftSmithWaterman.map_reads_calls`` (``Call``: pos in the reference
+    buffer ``ref``, kind, len, REF and ALT bases as the call changes them).  ``ref_name`` and ``ref_len`` as ``write_sam`` takes them;
+    as lists (one entry per contig) they want ``starts``, the contigs' first positions in ``ref``.  A ##contig line per contig;
+    FORMAT GT:GQ:DP:AD:PL.  An indel is anchored on the base in front of it, or on the base behind it at a contig's first position, as
+    the specification says.  Calls with gt == 0 or qual < ``min_qual`` are left out; a deletion run cut at max_del (flag 1) gets
+    FILTER LongDel, every other record PASS.  The genotypes are biallelic and unphased.  -> the number of records written."""
+    names, lens, many = _targets(ref_name, ref_len)
+    if many and (starts is None or len(starts) != len(names)):
+        raise ValueError("a reference of contigs wants starts: the first position of every contig")
+    first = [int(x) for x in (starts if many else [0])]
+
+    def contig_of(pos):
+        c = int(np.searchsorted(np.asarray(first, np.int64), pos, side="right")) - 1
+        return c if c >= 0 and pos - first[c] < lens[c] else -1
+
+    base = lambda at: bytes(ref[at:at + 1]).upper()  # noqa: E731
+    lines = []
+    for call in calls:
+        if call.gt == 0 or call.qual < min_qual:
+            continue
+        pos = int(call.pos)
+        c = contig_of(pos)
+        if call.kind == 1:
+            at, r, a = pos, bytes(call.ref), bytes(call.alt)
+        elif call.kind == 2:
+            if c >= 0 and pos > first[c]:
+                at, r, a = pos - 1, base(pos - 1) + bytes(call.ref), base(pos - 1)
+            else:                                                   # a contig's first base is deleted: the base behind
+                behind = base(pos + len(call.ref))
+                at, r, a = pos, bytes(call.ref) + behind, behind
+        elif c >= 0:
+            at, r, a = pos, base(pos), base(pos) + bytes(call.alt)
+        else:                                                       # inserted in front of a contig's first base: the base behind
+            c = contig_of(pos + 1)
+            if c < 0 or first[c] != pos + 1:
+                raise ValueError("insertion behind %d lies in no contig" % pos)
+            at, r, a = pos + 1, base(pos + 1), bytes(call.alt) + base(pos + 1)
+        if c < 0:
+            raise ValueError("call at %d lies in no contig" % pos)
+        fields = [names[c], str(at - first[c] + 1), ".", r.upper().decode(), a.upper().decode(), str(int(call.qual)), "LongDel" if call.flags & 1 else "PASS",
+                  ".", "GT:GQ:DP:AD:PL", "%s:%d:%d:%d,%d:%d,%d,%d" % ("0/1" if call.gt == 1 else "1/1", call.gq, call.depth, call.ref_count, call.alt_count,
+                                                                     *call.pl)]
+        lines.append((c, at, len(lines), "\t".join(fields)))
+    with open(path, "wt") as f:
+        f.write("##fileformat=VCFv4.2\n##source=mgl_amd\n")
+        f.write("".join("##contig=<ID=%s,length=%d>\n" % x for x in zip(names, lens)))
+        f.write('##FILTER=<ID=PASS,Description="All filters passed">\n')
+        f.write('##FILTER=<ID=LongDel,Description="The run of deleted positions goes on beyond max_del">\n')
+        f.write('##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">\n')
+        f.write('##FORMAT=<ID=GQ,Number=1,Type=Integer,Description="Genotype quality: the smaller PL of the other two genotypes, at most 99">\n')
+        f.write('##FORMAT=<ID=DP,Number=1,Type=Integer,Description="Depth at the position: bases and deleted columns">\n')
+        f.write('##FORMAT=<ID=AD,Number=R,Type=Integer,Description="Reads for the reference and for the alternate allele">\n')
+        f.write('##FORMAT=<ID=PL,Number=G,Type=Integer,Description="Phred-scaled genotype likelihoods from integer costs per read">\n')
+        f.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n" % sample)
+        for _, _, _, text in sorted(lines):
+            f.write(text + "\n")
+    return len(lines)
+
+
+def read_vcf(path):
+    """-> (the header lines, without their newline; [VcfRecord]) of a one-sample file as ``write_vcf`` writes it"""
+    header, records = [], []
+    with _open(path) as f:
+        for line in f:
+            line = line.rstrip("\n")
+            if line.startswith("#"):
+                header.append(line)
+                continue
+            if not line:
+                continue
+            c = line.split("\t")
+            sample = dict(zip(c[8].split(":"), c[9].split(":")))
+            ints = lambda x: tuple(int(v) for v in x.split(","))  # noqa: E731
+            records.append(VcfRecord(c[0], int(c[1]) - 1, c[3].encode(), c[4].encode(), int(c[5]), c[6], sample["GT"], int(sample["GQ"]), int(sample["DP"]),
+                                     ints(sample["AD"]), ints(sample["PL"])))
+    return header, records

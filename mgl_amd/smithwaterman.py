@@ -48,6 +48,11 @@ AlignmentStats = namedtuple("AlignmentStats", "n_match n_mismatch n_ins n_del n_
 RankedChain = namedtuple("RankedChain", "score strand n_anchors t_beg t_end q_beg q_end parent n_sub subsc mapq end_index")
 Line = namedtuple("Line", "ref_beg ref_end strand score cigar q_beg q_end flag mapq parent nm n_match block_len md xcigar rid rname status")
 AllMapResult = namedtuple("AllMapResult", "n_lines lines")
+Call = namedtuple("Call", "pos kind len ref alt depth ref_count alt_count gt gq qual pl flags")
+Call.__doc__ = ("one variant call (map_reads_calls): pos counts from 0 in the reference buffer; kind 1 SNV (ref and alt one base each), 2 deletion (ref the "
+                "deleted bases from pos on, alt empty), 3 insertion (ref empty, alt the inserted bases, which stand BEHIND pos); gt 0 = 0/0, 1 = 0/1, "
+                "2 = 1/1; pl = (PL0, PL1, PL2); flags 1: the deletion run was cut at max_del")
+GenotypeCosts = namedtuple("GenotypeCosts", "cost_match cost_error cost_het")
 IndexInfo = namedtuple("IndexInfo", "ref_len entries bytes k w")
 ContigTable = namedtuple("ContigTable", "names starts lens")
 ContigTable.__doc__ = "the contigs of an Index: names (a list of str), starts and lens (int64 arrays) in the reference buffer's coordinates"
@@ -56,6 +61,46 @@ ContigTable.__doc__ = "the contigs of an Index: names (a list of str), starts an
 ContigMapResult = namedtuple("ContigMapResult", MapResult._fields + ("rid", "rname"))
 ContigRankedMapResult = namedtuple("ContigRankedMapResult", RankedMapResult._fields + ("rid", "rname"))
 ContigDescribedMapResult = namedtuple("ContigDescribedMapResult", DescribedMapResult._fields + ("rid", "rname"))
+
+
+def genotype_costs(error_phred=20):
+    """The three integer costs of mgl_sw_genotype_sites_device, in 1/256 phred per read, for a per-base error of phred
+    ``error_phred``: what a read costs under a genotype it agrees with (cost_match), under one it contradicts (cost_error: the error
+    lands on ONE of the three other bases) and under a heterozygous one (cost_het).  For 20: (11, 6341, 778).  The device sees these
+    integers only; tests/calls_textbook.py takes them from here."""
+    import math
+
+    e = 10 ** (-error_phred / 10)
+    return GenotypeCosts(max(1, round(-2560 * math.log10(1 - e))), round(-2560 * math.log10(e / 3)), round(-2560 * math.log10((1 - e) / 2 + e / 6)))
+
+
+def _counted_lines(lines, min_mapq):
+    """the pileup's select, made on the device from the classify stage's line rows: a job is counted where it is a line (order >= 0), not
+    a secondary one (flag & 0x100 == 0) and its mapq is at least ``min_mapq``"""
+    return ((lines[:, 0] >= 0) & ((lines[:, 1] & 0x100) == 0) & (lines[:, 2] >= int(min_mapq))).to(lines.dtype)
+
+
+def _entry_costs(costs, error_phred):
+    """-> (cost_match, cost_het, cost_error) as the entry takes them: ``costs`` in that order, or genotype_costs(error_phred)"""
+    if costs is None:
+        c = genotype_costs(error_phred)
+        return c.cost_match, c.cost_het, c.cost_error
+    if isinstance(costs, GenotypeCosts):
+        return costs.cost_match, costs.cost_het, costs.cost_error
+    return tuple(int(c) for c in costs)
+
+
+def make_call(row, seq, ref, region_beg=0):
+    """mgl_sw_call's sixteen fields, the call's sequence row and the reference buffer -> Call"""
+    pos, kind, n, _, alt, depth, rc, ac, gt, gq, qual, pl0, pl1, pl2, flags = (int(v) for v in row[:15])
+    at = region_beg + pos
+    if kind == 1:
+        ra = bytes(ref[at:at + 1]), b"ACGTN"[alt:alt + 1]
+    elif kind == 2:
+        ra = bytes(ref[at:at + n]), b""
+    else:
+        ra = b"", bytes(bytearray(int(b) for b in seq[:n]))
+    return Call(pos, kind, n, ra[0], ra[1], depth, rc, ac, gt, gq, qual, (pl0, pl1, pl2), flags)
 
 
 class Index:
@@ -1451,7 +1496,7 @@ class MicrosoftSmithWaterman:
         stride = int(stages["cigar_stride"])
         res = self.map_reads_all_device(index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters, **stages)
         jobs, window, aln, lines = res[3], res[4], res[5], res[7][0]
-        select = ((lines[:, 0] >= 0) & ((lines[:, 1] & 0x100) == 0) & (lines[:, 2] >= int(min_mapq))).to(lines.dtype)
+        select = _counted_lines(lines, min_mapq)
         piled = self.pileup_device(index.ref, window[0], window[1], jobs[9], jobs[3], jobs[4], aln[0], aln[4], stride, aln[5], aln[6], select,
                                    (0, int(index.info.ref_len)), counts, binary)
         return res + (piled,)
@@ -1468,6 +1513,113 @@ class MicrosoftSmithWaterman:
                                            strands=strands, cigar_stride=stride, xcigar=False, **stages)
         torch.cuda.synchronize(dev)
         return self._all_result(index, n, stride, *res[3:8], False), res[8][0].cpu().numpy().view(np.uint32)
+
+    def pileup_insertions_device(self, targets, t_start, t_len, queries, q_start, q_len, aln, cigar, cigar_stride, cigar_len, sites, n_sites,
+                                 status_in=None, select=None, region_beg=0, max_ins=16, ins=None, binary_cigar=False, out=None):
+        """mgl_sw_pileup_insertions_batch_device on device tensors: ``pileup_device``'s alignments (give it exactly the tensors,
+        status and select the pileup took) and ``pileup_sites_device``'s sites [site_capacity, 8] and n_sites [1] int64, which stay on
+        the device (tests/calls_textbook.py); enqueued on the current stream, not synchronised.  Returns (ins [site_capacity,
+        6 * max_ins + 1] int32 -- the uint32 bits: word 0 the insertions longer than max_ins, word L those of L bases, then five
+        channel counts per column --, status [n]).  The entry ADDS: ``ins=None`` allocates zeros, a tensor given accumulates.
+        ``out``: an (ins, status) tuple to write into (its status may be None)."""
+        import torch
+
+        ctx = self._ensure()
+        n = int(t_start.numel())
+        dev = targets.device
+        cap = int(sites.numel()) // 8
+        width = 6 * int(max_ins) + 1
+        if out is None:
+            out = (torch.zeros((max(cap, 0), width), dtype=torch.int32, device=dev) if ins is None else ins, _alloc(dev)(n))
+        table, st = out
+        assert table.numel() >= cap * width and table.dtype == torch.int32 and table.is_contiguous() and sites.is_contiguous()
+        assert st is None or st.numel() >= n
+        ptr = _ptrs(dev)
+        rc = _lib.lib().mgl_sw_pileup_insertions_batch_device(
+            ctx, torch.cuda.current_stream(dev).cuda_stream, n, ptr(targets), ptr(t_start), ptr(t_len), ptr(queries), ptr(q_start), ptr(q_len), ptr(aln),
+            ptr(cigar), int(cigar_stride), ptr(cigar_len), ptr(status_in), ptr(select), int(region_beg), ptr(sites), ptr(n_sites), cap, int(max_ins),
+            ptr(table), ptr(st), _lib.FLAG_BINARY_CIGAR if binary_cigar else 0)
+        _check(rc, ctx)
+        return out
+
+    def genotype_sites_device(self, counts, ref, sites, n_sites, ins=None, region_beg=0, max_ins=16, max_del=64, error_phred=20, costs=None,
+                              call_capacity=None, out=None):
+        """mgl_sw_genotype_sites_device on device tensors: ``pileup_device``'s counts, the reference bytes, ``pileup_sites_device``'s
+        sites and n_sites and ``pileup_insertions_device``'s table (None: no insertion is called); enqueued on the current stream, not
+        synchronised.  ``costs``: (cost_match, cost_het, cost_error), by default ``genotype_costs(error_phred)``.  Returns (calls
+        [call_capacity, 16] int32 -- mgl_sw_call's fields, in site order --, n_calls [1] int64: the total, those beyond the capacity
+        included, seq [call_capacity, max_ins] uint8: an insertion call's bases and zeros behind them).  ``call_capacity`` defaults to
+        three per site slot; 0 is a sizing pass.  ``out``: such a tuple to write into, whose tensors decide what is written."""
+        import torch
+
+        ctx = self._ensure()
+        dev = counts.device
+        length = int(counts.numel()) // 8
+        slots = int(sites.numel()) // 8
+        if out is None:
+            cap = 3 * slots if call_capacity is None else int(call_capacity)
+            new = _alloc(dev)
+            out = (new((max(cap, 0), 16)), new(1, torch.int64), new((max(cap, 0), int(max_ins)), torch.uint8))
+        calls, nc, seq = out
+        cap = (int(calls.numel()) // 16 if calls is not None else 0) if call_capacity is None else int(call_capacity)
+        assert counts.is_contiguous() and sites.is_contiguous() and (calls is None or calls.numel() >= 16 * cap)
+        assert seq is None or seq.numel() >= cap * int(max_ins)
+        assert ins is None or (ins.is_contiguous() and ins.numel() >= slots * (6 * int(max_ins) + 1))
+        assert ref.numel() >= int(region_beg) + length
+        ptr = _ptrs(dev)
+        rc = _lib.lib().mgl_sw_genotype_sites_device(ctx, torch.cuda.current_stream(dev).cuda_stream, ptr(counts), length, ptr(ref), int(region_beg), ptr(sites),
+                                                     ptr(n_sites), slots, ptr(ins), int(max_ins), int(max_del), *_entry_costs(costs, error_phred), ptr(calls),
+                                                     cap, ptr(nc), ptr(seq))
+        _check(rc, ctx)
+        return out
+
+    def map_reads_calls_device(self, index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters=GATK_PARAMETERS, min_mapq=0, min_depth=4,
+                               min_alt=2, min_frac=64, site_capacity=None, max_ins=16, max_del=64, error_phred=20, costs=None, call_capacity=None,
+                               **stages):
+        """``map_reads_pileup_device``, then ``pileup_sites_device`` over its table, then ``pileup_insertions_device`` on exactly the
+        tensors the pileup took, then ``genotype_sites_device``: reads in, calls out, on the current stream, nothing read back and
+        nothing synchronised in between.  ONE batch: the insertion evidence needs the alignments AFTER the sites are known, and a
+        batch's alignments are gone when the next one is mapped.  ``site_capacity`` defaults to min(ref_len, 2^18) site slots.  Returns ``map_reads_pileup_device``'s nine tuples, then the sites'
+        tuple, the insertions' (ins, status) and the genotype's (calls, n_calls, seq)."""
+        binary = bool(stages.get("binary_cigar", False))
+        if stages.get("cigar_stride") is None:
+            stages["cigar_stride"] = _default_stride(max_tl, max_ql, binary)
+        stride = int(stages["cigar_stride"])
+        res = self.map_reads_pileup_device(index, queries, q_start, q_len, max_tl, max_ql, band, zdrop, parameters, min_mapq=min_mapq, **stages)
+        jobs, window, aln, lines, counts = res[3], res[4], res[5], res[7][0], res[8][0]
+        select = _counted_lines(lines, min_mapq)
+        if site_capacity is None:  # (a row of the insertion table per slot: not one per position of the reference)
+            site_capacity = min(int(index.info.ref_len), 1 << 18)
+        found = self.pileup_sites_device(counts, index.ref, 0, min_depth, min_alt, min_frac, site_capacity, call=False, flags=False)
+        ins = self.pileup_insertions_device(index.ref, window[0], window[1], jobs[9], jobs[3], jobs[4], aln[0], aln[4], stride, aln[5], found[2], found[3],
+                                            aln[6], select, 0, max_ins, None, binary)
+        called = self.genotype_sites_device(counts, index.ref, found[2], found[3], ins[0], 0, max_ins, max_del, error_phred, costs, call_capacity)
+        return res + (found, ins, called)
+
+    def map_reads_calls(self, index, reads, band=64, zdrop=-1, parameters=GATK_PARAMETERS, slack=200, strands=2, max_tl=None, min_mapq=0, min_depth=4,
+                        min_alt=2, min_frac=64, site_capacity=None, max_ins=16, max_del=64, error_phred=20, costs=None, **stages):
+        """``map_reads_calls_device`` over a list of byte strings.  Returns (AllMapResult as ``map_reads_all`` gives it, counts: a numpy
+        uint32 array [8, ref_len], calls: a list of ``Call`` in position order, whose REF / ALT bases are built here on the host from
+        the reference, the call's length and its sequence row).  It handles ONE batch: the insertion evidence needs the alignments
+        after the sites are known, so batches cannot accumulate into one call set without keeping their alignments."""
+        import torch
+
+        dev = torch.device("cuda", self._device)
+        n, packed, max_tl, max_ql, stride = _map_setup(reads, dev, slack, max_tl, stages)
+        res = self.map_reads_calls_device(index, *packed, max_tl, max_ql, band, zdrop, parameters, min_mapq=min_mapq, min_depth=min_depth, min_alt=min_alt,
+                                          min_frac=min_frac, site_capacity=site_capacity, max_ins=max_ins, max_del=max_del, error_phred=error_phred,
+                                          costs=costs, slack=slack, strands=strands, cigar_stride=stride, xcigar=False, **stages)
+        torch.cuda.synchronize(dev)
+        found, called = res[9], res[11]
+        total, slots = int(found[3][0]), int(found[2].shape[0])
+        if total > slots:
+            raise _lib.MglSwError(_lib.ERR_NOMEM, f"{total} candidate sites, site_capacity {slots}")
+        n_calls = int(called[1][0])
+        ref = index.ref.cpu().numpy().tobytes()
+        rows = called[0].cpu().numpy()[:n_calls]
+        seq = called[2].cpu().numpy()[:n_calls]
+        return (self._all_result(index, n, stride, *res[3:8], False), res[8][0].cpu().numpy().view(np.uint32),
+                [make_call(r, s, ref) for r, s in zip(rows, seq)])
 
     def align_packed_2bit(self, target_bases, target_base_count, t_start, t_len, query_bases, query_base_count, q_start, q_len,
                           max_tl, max_ql, parameters=GATK_PARAMETERS, overhang_strategy=SWOverhangStrategy.SOFTCLIP, cigar_stride=None,

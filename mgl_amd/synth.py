@@ -290,16 +290,39 @@ def variant_mapping_set(seed, ref_len=8000, read_len=1000, step=125, snvs=10, de
             planted.append(("D", pos, bytes(ref[pos:pos + dele])))
         else:
             planted.append(("I", pos, bytes(pick((ref[pos], ref[pos + 1])) for _ in range(ins))))
+    return bytes(ref), _tile(apply_variants(ref, planted), read_len, step), planted
+
+
+def apply_variants(ref, planted):
+    """the reference with ``planted`` (variant_mapping_set's, in position order) applied: a haplotype"""
     donor, shift = bytearray(ref), 0
     for kind, pos, what in planted:
         if kind == "X":
             donor[pos + shift] = what[0]
         elif kind == "D":
-            del donor[pos + shift:pos + shift + dele]
-            shift -= dele
+            del donor[pos + shift:pos + shift + len(what)]
+            shift -= len(what)
         else:
             donor[pos + shift + 1:pos + shift + 1] = what
-            shift += ins
-    donor = bytes(donor)
+            shift += len(what)
+    return bytes(donor)
+
+
+def _tile(donor, read_len, step):
     reads = [donor[s:s + read_len] for s in range(0, len(donor) - read_len + 1, step)]
-    return bytes(ref), [revcomp(r) if k % 2 else r for k, r in enumerate(reads)], planted
+    return [revcomp(r) if k % 2 else r for k, r in enumerate(reads)]
+
+
+def diploid_variant_set(seed, het="even", **kw):
+    """``variant_mapping_set(seed, **kw)``'s reference and donor as haplotype A, which carries every planted variant, and a haplotype
+    B that carries only the planted variants of the OTHER parity of index than ``het`` ("even" or "odd"): the variants whose index has
+    parity ``het`` are heterozygous, the others homozygous.  Reads tile both haplotypes as that function tiles its donor, A's first.
+    -> (ref, reads, planted, zygosity), zygosity[k] 1 where planted[k] is heterozygous and 2 where it is homozygous."""
+    if het not in ("even", "odd"):
+        raise ValueError('het is "even" or "odd"')
+    ref, reads, planted = variant_mapping_set(seed, **kw)
+    read_len, step = kw.get("read_len", 1000), kw.get("step", 125)
+    parity = 0 if het == "even" else 1
+    zygosity = [1 if k % 2 == parity else 2 for k in range(len(planted))]
+    hap_b = apply_variants(ref, [v for v, z in zip(planted, zygosity) if z == 2])
+    return ref, reads + _tile(hap_b, read_len, step), planted, zygosity
